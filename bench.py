@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- interpolated frames/s (+ ms per flow calc) of the HIP OpticalFlowCalc path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hdr2160_24to120] [--radius 16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hdr2160_24to120] [--radius 16] [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A STEP = `--periods-per-step` (64) consecutive source-frame periods for every one of the `--streams` independent
@@ -258,7 +258,38 @@ def parse_args():
     ap.add_argument("--content-counters", action="store_true", help="behind the timed region: device-side counters of a few periods (share of staged / "
                     "global / generic warp workgroups, share of windows that reused their SADs per level; include/hopperflow_diag.h)")
     ap.add_argument("--no-content-legs", action="store_true", help="skip the short legs of the other content classes behind the default workload")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="behind the timed region: write what the timed path computed in its last "
+                    "step to DIR/*.npy (float32 / float64, under 64 MB; see dump_outputs()), to compare two builds output for output")
     return ap.parse_args()
+
+
+DUMP_SAMPLE_BYTES = 48 << 20   # --dump-outputs: the float32 sample of the output frames; the other arrays are small, the dump stays under 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, calcs, outbufs, ts, hdr):
+    """--dump-outputs: what a caller of the timed path received in the last source period of the last timed step (every period
+    writes the same output buffers, so the step's earlier periods are gone), for every pair stream of this rank:
+      output_frames_sample.npy   float32 [streams, outputs of the period, k]: the same fixed, seeded k elements of every output frame
+                                 (all of them when they fit the budget)
+      output_sample_index.npy    float64 [k]: which elements of the flat frame (Y plane then UV plane) the sample holds
+      blend_scalars.npy          float64 [outputs of the period]: the blending scalar t of each output frame
+      total_frame_delta.npy      float64 [streams]: m_totalFrameDelta of each stream's last flow calculation
+    The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dt = np.dtype(np.uint16 if hdr else np.uint8)
+    elems = calcs[0].output_frame_bytes // dt.itemsize
+    k = min(elems, DUMP_SAMPLE_BYTES // (4 * len(calcs) * max(1, len(ts))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(elems, size=k, replace=False))
+    frames = np.empty((len(calcs), len(ts), k), np.float32)
+    for s in range(len(calcs)):
+        for j in range(len(ts)):
+            frames[s, j] = outbufs[s][j].download(dt, elems)[idx]
+    np.save(os.path.join(out_dir, "output_frames_sample.npy"), frames)
+    np.save(os.path.join(out_dir, "output_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "blend_scalars.npy"), np.asarray(ts, np.float64))
+    np.save(os.path.join(out_dir, "total_frame_delta.npy"), np.array([c.m_totalFrameDelta for c in calcs], np.float64))
 
 
 def cpu_baseline(hdr, H, W, target, radius, neighbor, frames, n_pairs):
@@ -667,6 +698,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if rank == 0:
         dev_mid.append(device_sample(sysfs))
+        if a.dump_outputs:     # before the burst below writes the same output buffers again; every stream follows one schedule
+            dump_outputs(a.dump_outputs, calcs, outbufs, schedule[(a.warmup + a.steps) * P - 1], hdr)
     # What the host loop itself costs: BURST periods issued into EMPTY queues (nothing blocks), per native call
     tb = time.perf_counter()
     for i in range((a.warmup + a.steps) * P, (a.warmup + a.steps) * P + BURST):
