@@ -19,6 +19,8 @@ HF_FLAG_BATCH_NORMAL_PRIORITY = 0x800
 HF_FLAG_BATCH_EAGER_PLANES = 0x1000
 HF_FLAG_NO_SAD_REUSE = 0x2000
 HF_FLAG_SAD_REUSE_ALWAYS = 0x4000
+HF_FLAG_PLANAR_IN = 0x8000      # frames handed to the context are planar 4:2:0 (yuv420p / yuv420p10le)
+HF_FLAG_PLANAR_OUT = 0x10000    # frames handed back are planar 4:2:0
 HF_MAX_PERIOD_OUTPUTS = 6
 
 (HF_OK, HF_ERR_INVALID_ARGUMENT, HF_ERR_NO_DEVICE, HF_ERR_OUT_OF_MEMORY, HF_ERR_HIP, HF_ERR_STATE) = (0, -1, -2, -3, -4, -5)
@@ -151,6 +153,7 @@ SIGNATURES = {
     "hf_set_profile_interval": (_i, [_vp, _i, _i]),
     "hf_timer_begin": (_i, [_vp]),
     "hf_timer_end": (_i, [_vp, C.POINTER(C.c_float)]),
+    "hf_planar_convert_device": (_i, [_vp, _i, _vp, _vp]),
     "hf_shard_timeline": (_i, [C.c_int64, _i, _i, C.c_int64, C.c_int64, _i, _i, C.POINTER(HfTimelineChunk), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int64]),
     "hf_hostio_create": (_i, [_vp, C.POINTER(HfHostioConfig), C.POINTER(_vp)]),
     "hf_hostio_destroy": (None, [_vp]),

@@ -15,7 +15,10 @@
         `--gpus 1` runs the same streaming path in one worker; without --gpus the blocking reference protocol is used.
 
 Input: contiguous frames, Y plane then interleaved UV (8-bit NV12, or 16-bit little-endian P010 with --hdr), or a
-YUV4MPEG2 stream (C420* / C420p10, see y4m.py) when the name ends in .y4m.
+YUV4MPEG2 stream (C420* / C420p10, see y4m.py) when the name ends in .y4m.  `--pix-fmt yuv420p | yuv420p10le` (ffmpeg's names,
+e.g. `ffmpeg -i clip.mkv -pix_fmt yuv420p -f rawvideo in.yuv`) makes the raw sides planar Y, U, V planes instead; the 10-bit
+formats imply --hdr.  Planar frames, .y4m ones included, are re-laid on the device (HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT), not
+on the host.
 Output: the frames the DirectShow filter would deliver, in order (first two periods are copies,
 reference HopperRender.cpp:955,1179), two source frames late like the filter (`:940`).
 """
@@ -70,14 +73,18 @@ class _Clip:
             if self.f.read(6) != b"FRAME\n":
                 raise SystemExit("--gpus needs a .y4m file with plain FRAME records (no per-frame parameters)")
 
-    def read_into(self, k, out):
-        """Source frame k as NV12 / P010 into `out` (e.g. a pinned buffer)."""
+    def read_raw_into(self, k, out):
+        """Source frame k as stored in the file (NV12 / P010, or planar: .y4m and --pix-fmt yuv420p*) into `out` (e.g. a pinned buffer)."""
         self.f.seek(self.data0 + k * self.record + (6 if self.y4m else 0))
+        got = self.f.readinto(memoryview(out).cast("B")[:self.frame_bytes])
+        if got != self.frame_bytes:
+            raise IOError("short read")
+
+    def read_into(self, k, out):
+        """Source frame k as NV12 / P010 into `out` (a .y4m frame re-laid on the host; the workers read_raw_into a planar context)."""
         if not self.y4m:
-            got = self.f.readinto(memoryview(out).cast("B"))
-            if got != self.frame_bytes:
-                raise IOError("short read")
-            return
+            return self.read_raw_into(k, out)
+        self.f.seek(self.data0 + k * self.record + 6)
         p = np.frombuffer(self.f.read(self.frame_bytes), dtype=self.dt)
         H, W = self.height, self.width
         from .y4m import planar_to_semiplanar
@@ -98,7 +105,6 @@ def _worker(a, rank, world):
     from . import capi
     from .batch import shard_timeline
     from .hostio import HostIoRunner
-    from .y4m import semiplanar_to_planar
     clip = _Clip(a.input, a.width, a.height, a.hdr, a.source_fps)
     src_t, tgt_t = int(round(1e7 / clip.source_fps)), int(round(1e7 / a.target_fps))
     chunk = shard_timeline(clip.n_frames, world, rank, src_t, tgt_t)
@@ -107,7 +113,7 @@ def _worker(a, rank, world):
     record = clip.frame_bytes + (6 if out_y4m else 0)
     n_dev = max(1, capi.load().hf_device_count())
     runner = HostIoRunner(clip.hdr, clip.height, clip.width, device_index=(a.device + rank) % n_dev, delta_scalar=a.delta,
-                          neighbor_scalar=a.neighbor, black=a.black, white=a.white, search_radius=a.radius)
+                          neighbor_scalar=a.neighbor, black=a.black, white=a.white, search_radius=a.radius, flags=_planar_flags(a))
     fd = os.open(a.output, os.O_WRONLY)
     copies = 0
 
@@ -115,14 +121,10 @@ def _worker(a, rank, world):
         nonlocal copies
         copies += kind == "copy"
         off = head + (chunk.first_output + i) * record
-        if out_y4m:
-            y, u, v = semiplanar_to_planar(frame, clip.height, clip.width, clip.hdr)
-            data = b"FRAME\n" + b"".join(np.ascontiguousarray(p, dtype=clip.dt).tobytes() for p in (y, u, v))
-        else:
-            data = memoryview(frame).cast("B")
-        os.pwrite(fd, data, off)
+        data = memoryview(frame).cast("B")[:clip.frame_bytes]   # planar already when the output is .y4m (HF_FLAG_PLANAR_OUT)
+        os.pwritev(fd, [b"FRAME\n", data] if out_y4m else [data], off)
 
-    kinds = runner.run(chunk, clip.read_into, sink, a.mode, a.scene_threshold, src_t, tgt_t) if chunk.n_periods else []
+    kinds = runner.run(chunk, clip.read_raw_into, sink, a.mode, a.scene_threshold, src_t, tgt_t) if chunk.n_periods else []
     os.close(fd)
     runner.close()
     print(f"rank {rank}/{world} device {(a.device + rank) % n_dev}: source periods {chunk.first_period}..{chunk.first_period + chunk.n_periods - 1} "
@@ -154,11 +156,29 @@ def _multi_gpu(a, argv):
     print(f"{clip.n_frames} source frames -> {n_out} output frames on {a.gpus} GPU worker(s)", file=sys.stderr)
 
 
-def main(argv=None):
+PIX_FMTS = {"nv12": (False, False), "p010": (True, False), "yuv420p": (False, True), "yuv420p10le": (True, True)}   # (10-bit, planar)
+
+
+def _planar_flags(a):
+    """Context flags of a run: a .y4m side, or a raw side in a planar --pix-fmt, takes / returns planar frames."""
+    from . import capi
+    raw_planar = PIX_FMTS[a.pix_fmt][1]
+    flags = 0
+    if a.input.lower().endswith(".y4m") or raw_planar:
+        flags |= capi.HF_FLAG_PLANAR_IN
+    if a.output.lower().endswith(".y4m") or raw_planar:
+        flags |= capi.HF_FLAG_PLANAR_OUT
+    return flags
+
+
+def parse_args(argv=None):
+    """The command line; --pix-fmt defaults to nv12 / p010 (by --hdr), and a 10-bit format implies --hdr."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input"); ap.add_argument("output")
     ap.add_argument("--width", type=int); ap.add_argument("--height", type=int)
     ap.add_argument("--hdr", action="store_true")
+    ap.add_argument("--pix-fmt", choices=sorted(PIX_FMTS), default=None,
+                    help="layout of the raw sides: nv12 / p010 (default, by --hdr) or planar yuv420p / yuv420p10le (10-bit formats imply --hdr)")
     ap.add_argument("--source-fps", type=float, default=None, help="default: 23.976, or the .y4m header's rate"); ap.add_argument("--target-fps", type=float, default=60.0)
     ap.add_argument("--mode", type=int, default=2, help="frame output mode 0-6 (HopperRender.h:10-18)")
     ap.add_argument("--radius", type=int, default=16); ap.add_argument("--delta", type=int, default=8)
@@ -168,6 +188,17 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=0, help="N worker processes, one per GPU, asynchronous host I/O (0: the blocking reference protocol in this process)")
     ap.add_argument("--rank", type=int, default=-1, help=argparse.SUPPRESS); ap.add_argument("--world", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.pix_fmt is None:
+        a.pix_fmt = "p010" if a.hdr else "nv12"
+    elif PIX_FMTS[a.pix_fmt][0]:
+        a.hdr = True
+    elif a.hdr:
+        ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
+    return ap, a
+
+
+def main(argv=None):
+    ap, a = parse_args(argv)
     if a.rank >= 0:
         return _worker(a, a.rank, a.world)
     if a.gpus > 0:
@@ -175,7 +206,7 @@ def main(argv=None):
     with open(a.input, "rb") as fi, open(a.output, "wb") as fo:
         reader = None
         if a.input.lower().endswith(".y4m"):
-            reader = Y4MReader(fi)
+            reader = Y4MReader(fi, planar=True)
             a.width, a.height, a.hdr = reader.width, reader.height, reader.hdr
             if a.source_fps is None:
                 a.source_fps = reader.fps
@@ -190,13 +221,14 @@ def main(argv=None):
             r = Fraction(a.target_fps).limit_denominator(1001)
             writer = Y4MWriter(fo, a.width, a.height, r.numerator, r.denominator, a.hdr, reader.extra if reader else ())
         cls = OpticalFlowCalcHDR if a.hdr else OpticalFlowCalcSDR
-        calc = cls(a.height, a.width, 0, 0, a.delta, a.neighbor, a.black, a.white, 270, device_index=a.device, search_radius=a.radius)
+        calc = cls(a.height, a.width, 0, 0, a.delta, a.neighbor, a.black, a.white, 270, device_index=a.device, search_radius=a.radius,
+                   flags=_planar_flags(a))
         replay = FilterReplay(calc, int(round(1e7 / a.source_fps)), int(round(1e7 / a.target_fps)), a.mode, a.scene_threshold)
         n_in = n_out = 0
         for src in frames:
             for frame in replay.deliver(src):
                 if writer:
-                    writer.write(frame)
+                    writer.write_planar(frame)
                 else:
                     fo.write(frame.tobytes())
                 n_out += 1

@@ -24,6 +24,22 @@ int io_init(hf_ctx* c) {
 }
 
 // Before a warp/copy writes into an output-ring slot: wait for the asynchronous readback that still uses it.
+// HF_FLAG_PLANAR_IN / _OUT stages (hf_ctx.h), allocated on first use
+int ensure_in_stage(hf_ctx* c) {
+    for (auto& p : c->in_stage) if (!p) HF_HIP(c, hipMalloc(&p, c->in_bytes));
+    return HF_OK;
+}
+
+int ensure_out_stage(hf_ctx* c) {
+    for (auto& p : c->out_stage) if (!p) HF_HIP(c, hipMalloc(&p, c->out_bytes));
+    return HF_OK;
+}
+
+int out_slot(const hf_ctx* c, const void* target) {   // the output-ring slot `target` is, 0 if none
+    for (int i = 0; i < hf_ctx::kOutRing; i++) if (c->out_ring[i] && target == c->out_ring[i]) return i;
+    return 0;
+}
+
 int guard_output_slot(hf_ctx* c, const void* target, hipStream_t launch_stream) {
     if (!c->io_out) return HF_OK;
     for (int i = 0; i < hf_ctx::kOutRing; i++)
@@ -53,9 +69,11 @@ int hf_update_frame_async(hf_ctx* c, const void* pinned_host_frame) {
     if (int rc = io_init(c)) return rc;
     // the slot about to be overwritten holds the oldest frame: its last readers are the warp/copy launches
     // issued so far and its own (three updates old) phase-plane build
+    // (HF_FLAG_PLANAR_IN: the frame lands in the stage of that slot, whose last reader is the same re-layout launch in front of that build)
+    if (c->planar_in()) if (int rc = ensure_in_stage(c)) return rc;
     if (c->have_last_launch) HF_HIP(c, hipStreamWaitEvent(c->io_in, c->ev_last_launch, 0));
     HF_HIP(c, hipStreamWaitEvent(c->io_in, c->ev_slot_prep[0], 0));
-    HF_HIP(c, hipMemcpyAsync(c->ring_store[0], pinned_host_frame, c->in_bytes, hipMemcpyHostToDevice, c->io_in));
+    HF_HIP(c, hipMemcpyAsync(c->planar_in() ? c->in_stage[0] : c->ring_store[0], pinned_host_frame, c->in_bytes, hipMemcpyHostToDevice, c->io_in));
     HF_HIP(c, hipEventRecord(c->ev_h2d, c->io_in));
     if (int rc = leave_warp_stream(c)) return rc;
     if (c->timing()) {
@@ -64,6 +82,7 @@ int hf_update_frame_async(hf_ctx* c, const void* pinned_host_frame) {
     }
     HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
     c->ring[0] = c->ring_store[0];
+    if (c->planar_in()) hf::launch_planar_in(c->g.hdr, c->g.H, c->g.in_stride, c->in_stage[0], c->ring[0], c->stream);
     hf::launch_prep_frame(c->g, c->pl, c->ring[0], c->pp[0], c->stream);
     c->plane_pending[0] = false;
     HF_HIP(c, hipGetLastError());
@@ -81,7 +100,17 @@ int hf_download_frame_async(hf_ctx* c, void* pinned_host_out) {
     hipStream_t last = c->on_warp_stream ? c->warp_stream : c->stream;   // where the frame was just produced
     HF_HIP(c, hipEventRecord(c->ev_out_ready, last));
     HF_HIP(c, hipStreamWaitEvent(c->io_out, c->ev_out_ready, 0));
-    HF_HIP(c, hipMemcpyAsync(pinned_host_out, c->out_target, c->out_bytes, hipMemcpyDeviceToHost, c->io_out));
+    const void* from = c->out_target;
+    if (c->planar_out()) {
+        // re-layout on the readback stream into the stage paired with the output slot: the next conversion into that stage is issued
+        // behind this readback on the same stream, and the next warp into the slot waits for ev_d2h[slot], recorded behind both
+        if (int rc = ensure_out_stage(c)) return rc;
+        void* st = c->out_stage[out_slot(c, c->out_target)];
+        hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, c->out_target, st, c->io_out);
+        HF_HIP(c, hipGetLastError());
+        from = st;
+    }
+    HF_HIP(c, hipMemcpyAsync(pinned_host_out, from, c->out_bytes, hipMemcpyDeviceToHost, c->io_out));
     HF_HIP(c, hipEventRecord(c->ev_dl[c->dl_issued % hf_ctx::kDlRing], c->io_out));
     c->dl_issued++;
     for (int i = 0; i < hf_ctx::kOutRing; i++)
@@ -93,6 +122,17 @@ int hf_download_frame_async(hf_ctx* c, void* pinned_host_out) {
             break;
         }
     c->warp_started = false;
+    return HF_OK;
+}
+
+int hf_planar_convert_device(hf_ctx* c, int to_planar, const void* device_src, void* device_dst) {
+    HF_CHECK_CTX(c);
+    if (!device_src || !device_dst) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_planar_convert_device: null buffer");
+    if (int rc = set_device(c)) return rc;
+    if (to_planar) hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, device_src, device_dst, c->stream);
+    else hf::launch_planar_in(c->g.hdr, c->g.H, c->g.in_stride, device_src, device_dst, c->stream);
+    HF_HIP(c, hipGetLastError());
+    if (!c->async()) return sync_ctx(c);
     return HF_OK;
 }
 

@@ -128,6 +128,8 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     for (int i = 0; i < n; i++) {
         hf_ctx* m = members[i];
         if (!m) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: null member");
+        if (m->planar_in() || m->planar_out())
+            return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT contexts cannot join a batch");
         for (int j = 0; j < i; j++) if (members[j] == m) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: duplicate member");
         if (m->batch) return batch_fail(nullptr, HF_ERR_STATE, "hf_batch_create: member " + std::to_string(i) + " already belongs to a batch");
         const hf::Geom &a = l->g, &b = m->g;

@@ -214,6 +214,8 @@ int rotate_after_upload(hf_ctx* c) {
     c->ring_store[0] = c->ring_store[1]; c->ring_store[1] = c->ring_store[2]; c->ring_store[2] = fs;
     hipEvent_t es = c->ev_slot_prep[0];
     c->ev_slot_prep[0] = c->ev_slot_prep[1]; c->ev_slot_prep[1] = c->ev_slot_prep[2]; c->ev_slot_prep[2] = es;
+    void* st = c->in_stage[0];   // (HF_FLAG_PLANAR_IN) the stage a slot was converted from travels with it: ev_slot_prep guards both
+    c->in_stage[0] = c->in_stage[1]; c->in_stage[1] = c->in_stage[2]; c->in_stage[2] = st;
     uint32_t* pp = c->pp[0];
     const bool pend = c->plane_pending[0];
     c->ring[0] = c->ring[1]; c->pp[0] = c->pp[1]; c->plane_pending[0] = c->plane_pending[1];
@@ -224,7 +226,8 @@ int rotate_after_upload(hf_ctx* c) {
     return HF_OK;
 }
 
-// by_reference: the ring slot points at the caller's device frame instead of receiving a copy
+// by_reference: the ring slot points at the caller's device frame instead of receiving a copy (not under HF_FLAG_PLANAR_IN: the
+// slot receives the converted frame)
 int update_common(hf_ctx* c, const void* src, hipMemcpyKind kind, bool by_reference) {
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
@@ -232,7 +235,16 @@ int update_common(hf_ctx* c, const void* src, hipMemcpyKind kind, bool by_refere
         HF_HIP(c, hipEventRecord(c->ev_upload, c->stream));  // m_ofcStartedEvent (:20)
         c->upload_recorded = true;
     }
-    if (by_reference) {
+    if (c->planar_in()) {
+        c->ring[0] = c->ring_store[0];
+        const void* planar = src;
+        if (kind == hipMemcpyHostToDevice) {   // one H2D of the whole frame into a stage, then the re-layout into the slot
+            if (int rc = ensure_in_stage(c)) return rc;
+            HF_HIP(c, hipMemcpyAsync(c->in_stage[0], src, c->in_bytes, kind, c->stream));
+            planar = c->in_stage[0];
+        }
+        hf::launch_planar_in(c->g.hdr, c->g.H, c->g.in_stride, planar, c->ring[0], c->stream);
+    } else if (by_reference) {
         c->ring[0] = const_cast<void*>(src);
     } else {
         c->ring[0] = c->ring_store[0];
@@ -305,7 +317,21 @@ void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPe
 int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind) {
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
-    if (c->out_target != dst) HF_HIP(c, hipMemcpyAsync(dst, c->out_target, c->out_bytes, kind, c->stream));
+    if (c->planar_out()) {
+        if (kind == hipMemcpyDeviceToDevice) {
+            hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, c->out_target, dst, c->stream);
+        } else {   // re-layout into the stage paired with the output slot, then one D2H
+            if (int rc = ensure_out_stage(c)) return rc;
+            void* st = c->out_stage[out_slot(c, c->out_target)];
+            if (c->dl_issued)   // an asynchronous readback (hf_download_frame_async) may still read that stage
+                HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_dl[(c->dl_issued - 1) % hf_ctx::kDlRing], 0));
+            hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, c->out_target, st, c->stream);
+            HF_HIP(c, hipMemcpyAsync(dst, st, c->out_bytes, kind, c->stream));
+        }
+        HF_HIP(c, hipGetLastError());
+    } else if (c->out_target != dst) {
+        HF_HIP(c, hipMemcpyAsync(dst, c->out_target, c->out_bytes, kind, c->stream));
+    }
     if (c->timing()) HF_HIP(c, hipEventRecord(c->ev_warp_end, c->stream));
     if (kind == hipMemcpyDeviceToHost || !c->async()) {
         if (int rc = sync_ctx(c)) return rc;
@@ -427,6 +453,20 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
                              int update_and_flow) {
     HF_CHECK_CTX(c);
     if (n_out < 0 || (n_out > 0 && (!t || !device_out))) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_interpolate_period: bad argument");
+    // HF_FLAG_PLANAR_OUT: the warps write semi-planar frames into stages of the context, converted into the caller's buffers at the end
+    std::vector<void*> staged;
+    void* const* const caller_out = device_out;
+    if (c->planar_out() && n_out > 0) {
+        if (int rc = set_device(c)) return rc;
+        while ((int)c->period_stage.size() < n_out) {
+            void* p = nullptr;
+            HF_HIP(c, hipMalloc(&p, c->out_bytes));
+            c->period_stage.push_back(p);
+        }
+        staged.assign(device_out, device_out + n_out);
+        for (int i = 0; i < n_out; i++) if (staged[i]) staged[i] = c->period_stage[(size_t)i];
+        device_out = staged.data();
+    }
     if (update_and_flow) {
         if (device_frame) if (int rc = hf_update_frame_device_ref(c, device_frame)) return rc;
         if (int rc = hf_calculate_optical_flow(c)) return rc;
@@ -473,6 +513,12 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
     c->in_period = false;
     c->out_target = saved;
     if (rc == HF_OK && done < n_out && c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
+    if (rc == HF_OK && !staged.empty()) {   // behind the warps, on their stream
+        for (int i = 0; i < n_out; i++)
+            if (caller_out[i]) hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, staged[(size_t)i], caller_out[i], c->warp_stream);
+        HF_HIP(c, hipGetLastError());
+        if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
+    }
     return rc;
 }
 
@@ -490,6 +536,8 @@ int hf_download_frame_device(hf_ctx* c, void* device_out) {
 
 int hf_set_output_buffer(hf_ctx* c, void* device_out) {
     HF_CHECK_CTX(c);
+    if (device_out && c->planar_out())
+        return fail(c, HF_ERR_STATE, "hf_set_output_buffer: the kernels write NV12 / P010 frames; under HF_FLAG_PLANAR_OUT use hf_download_frame_device");
     c->out_target = device_out ? device_out : c->out_frame;
     return HF_OK;
 }

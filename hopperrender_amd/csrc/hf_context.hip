@@ -197,6 +197,10 @@ int hf_create(const hf_config* cfg, hf_ctx** out_ctx) {
         delete c;
         return fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_create: strides must be >= frame width");
     }
+    if (((cfg->flags & HF_FLAG_PLANAR_IN) && (g.in_stride & 1)) || ((cfg->flags & HF_FLAG_PLANAR_OUT) && (g.out_stride & 1))) {
+        delete c;   // the U and V planes of a planar frame are S/2 elements wide
+        return fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_create: a planar side needs an even stride (input %d, output %d)", g.in_stride, g.out_stride);
+    }
     if (c->cfg.blur_radius <= 0) c->cfg.blur_radius = 4;               // blurFlowKernelSDR.h:4
     if (c->cfg.blur_radius > 64) { delete c; return fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_create: blur_radius must be <= 64"); }
     c->p.delta_scalar = cfg->delta_scalar;
@@ -357,6 +361,9 @@ void hf_destroy(hf_ctx* c) {
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
     if (c->io_in) { hipStreamSynchronize(c->io_in); hipStreamSynchronize(c->io_out); hipStreamDestroy(c->io_in); hipStreamDestroy(c->io_out); }
     for (int i = 1; i < hf_ctx::kOutRing; i++) if (c->out_ring[i]) hipFree(c->out_ring[i]);
+    for (void* p : c->in_stage) if (p) hipFree(p);
+    for (void* p : c->out_stage) if (p) hipFree(p);
+    for (void* p : c->period_stage) if (p) hipFree(p);
     for (hipEvent_t e : {c->ev_h2d, c->ev_last_launch, c->ev_out_ready}) if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_slot_prep) if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_d2h) if (e) hipEventDestroy(e);
@@ -551,8 +558,9 @@ int hf_debug_bounds_violations(hf_ctx* c, uint32_t* count, uint32_t first[4], in
     if (int rc = set_device(c)) return rc;
     if (hipDeviceSynchronize() != hipSuccess) return fail(c, HF_ERR_HIP, "hf_debug_bounds_violations: hipDeviceSynchronize failed");
     unsigned rec[5] = {0, 0, 0, 0, 0};
-    const bool a = hf::dbg_bounds_read_kernels(rec, reset != 0), b = hf::dbg_bounds_read_flow(rec, reset != 0);
-    if (!a || !b) return fail(c, HF_ERR_STATE, "hf_debug_bounds_violations: this library was built without -DHF_DEBUG_BOUNDS (python -m hopperrender_amd.build --debug-bounds)");
+    const bool a = hf::dbg_bounds_read_kernels(rec, reset != 0), b = hf::dbg_bounds_read_flow(rec, reset != 0),
+               p = hf::dbg_bounds_read_planar(rec, reset != 0);
+    if (!a || !b || !p) return fail(c, HF_ERR_STATE, "hf_debug_bounds_violations: this library was built without -DHF_DEBUG_BOUNDS (python -m hopperrender_amd.build --debug-bounds)");
     *count = rec[0];
     if (first) for (int i = 0; i < 4; i++) first[i] = rec[1 + i];
     return HF_OK;

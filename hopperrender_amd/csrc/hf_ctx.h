@@ -121,6 +121,13 @@ struct hf_ctx {
     hipEvent_t ev_flow_done = nullptr;                 // behind the last chain of an asynchronous context (hf_wait_flow)
     bool flow_done_recorded = false;
 
+    // planar frames at the boundary (HF_FLAG_PLANAR_IN / _OUT, hf_planar.hip); every buffer is allocated on first use
+    void* in_stage[3] = {nullptr, nullptr, nullptr};             // planar host frames land here (rotates with ring_store / ev_slot_prep)
+    void* out_stage[kOutRing] = {nullptr, nullptr, nullptr};     // planar frames the readbacks read ([i] paired with out_ring[i])
+    std::vector<void*> period_stage;                             // semi-planar targets of hf_interpolate_period's warps
+    bool planar_in() const { return (cfg.flags & HF_FLAG_PLANAR_IN) != 0; }
+    bool planar_out() const { return (cfg.flags & HF_FLAG_PLANAR_OUT) != 0; }
+
     int ring_phase = 0;   // number of rotations mod 3 (graph key)
     int blur_phase = 0;   // number of swaps mod 2
     bool have_flow = false;
@@ -217,6 +224,9 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
 
 // hf_async_io.hip
 int io_init(hf_ctx* c);
+int ensure_in_stage(hf_ctx* c);
+int ensure_out_stage(hf_ctx* c);
+int out_slot(const hf_ctx* c, const void* target);
 int guard_output_slot(hf_ctx* c, const void* target, hipStream_t launch_stream);
 int note_launch(hf_ctx* c, hipStream_t launch_stream);
 

@@ -236,6 +236,12 @@ void launch_warp(const Geom& g, const void* frame12, const void* frame21, const 
                  hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);  // events: timestamps of the dispatch itself
 // copyFrameKernel, both planes in one launch.
 void launch_copy(const Geom& g, const void* src, void* out, float black, float white, hipStream_t stream);
+// Planar 4:2:0 frames at the device boundary (hf_planar.hip; HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT): planar (Y, U, V planes) <-> the
+// semi-planar NV12 / P010 frame, H rows of `stride` elements, padding included; HDR values are LSB-aligned on the planar side (<< 6 in,
+// >> 6 out, wrapping in 16 bits).  Source and destination must not overlap.
+void launch_planar_in(int hdr, int H, int stride, const void* planar, void* semi, hipStream_t stream);
+void launch_planar_out(int hdr, int H, int stride, const void* semi, void* planar, hipStream_t stream);
+bool dbg_bounds_read_planar(unsigned out[5], bool reset);
 // Debug-bounds records of the two kernel translation units (hf_kernels.hip / hf_flow.hip): out[0] += violations, out[1..4] = the first
 // one's site / block / thread / source line; reset: zero the records.  Return false in a build without HF_DEBUG_BOUNDS.
 bool dbg_bounds_read_kernels(unsigned out[5], bool reset);

@@ -46,13 +46,14 @@ def shard_timeline_native(n_source_frames, world, rank, source_frame_time=SOURCE
 class HostIoRunner:
     """One asynchronous context + the native driver (hf_hostio_*, csrc/hf_hostio.cpp) with its pinned rings.
     `fill(k, array)` writes source frame k of the clip into `array` (a view of a page-locked buffer: a file reader reads
-    straight into it); `sink(i, array, kind)` receives the rank's i-th output frame ('warp' | 'copy'; valid only during the call)."""
+    straight into it); `sink(i, array, kind)` receives the rank's i-th output frame ('warp' | 'copy'; valid only during the call).
+    `flags` is OR-ed into the context's flags, e.g. capi.HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT for planar 4:2:0 frames in `fill` / `sink`."""
 
     def __init__(self, hdr, height, width, *, device_index=0, delta_scalar=8, neighbor_scalar=6, black=0.0, white=255.0,
-                 search_radius=16, blur_radius=0, in_ring=3, out_ring=12):
+                 search_radius=16, blur_radius=0, in_ring=3, out_ring=12, flags=0):
         cls = OpticalFlowCalcHDR if hdr else OpticalFlowCalcSDR
         self.calc = cls(height, width, 0, 0, delta_scalar, neighbor_scalar, black, white, 270, device_index=device_index,
-                        search_radius=search_radius, blur_radius=blur_radius, flags=capi.HF_FLAG_ASYNC | capi.HF_FLAG_DUAL_STREAM)
+                        search_radius=search_radius, blur_radius=blur_radius, flags=capi.HF_FLAG_ASYNC | capi.HF_FLAG_DUAL_STREAM | int(flags))
         self._lib = capi.load()
         self.in_ring, self.out_ring = int(in_ring), int(out_ring)
         dt = np.dtype(self.calc.dtype)

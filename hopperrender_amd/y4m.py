@@ -5,7 +5,9 @@ reference HopperRender.cpp:603-625 media types); Y4M stores planar 4:2:0, so fra
     C420 / C420jpeg / C420mpeg2 / C420paldv   Y, U, V planes of uint8       <->  NV12
     C420p10                                   Y, U, V planes of LE uint16   <->  P010 (code << 6)
 
-Only the host-side byte shuffling lives here; nothing in this module touches the device.
+Only the host-side byte shuffling lives here; nothing in this module touches the device.  A context created with
+HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT (include/hopperflow.h) takes and returns the planar frames themselves, re-laid on the
+device: Y4MReader(..., planar=True) / read_planar() and Y4MWriter.write_planar() move them unconverted.
 """
 import numpy as np
 
@@ -41,10 +43,12 @@ def semiplanar_to_planar(frame, H, W, hdr):
 
 
 class Y4MReader:
-    """Iterates the frames of a .y4m stream as NV12 / P010 arrays."""
+    """Iterates the frames of a .y4m stream as NV12 / P010 arrays, or -- planar=True -- as the file's planar frames (1-D uint8 /
+    little-endian uint16 arrays: Y, U, V planes as stored, 10-bit values LSB-aligned)."""
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, planar=False):
         self.f = fileobj
+        self.planar = planar
         head = self._line()
         tok = head.split(b" ")
         if tok[0] != b"YUV4MPEG2":
@@ -98,19 +102,27 @@ class Y4MReader:
     def __iter__(self):
         return self
 
-    def __next__(self):
+    def read_planar(self):
+        """The next frame's planar data as stored (1-D: Y, U, V planes), or None at the end of the stream."""
         head = self._line()
         if not head:
-            raise StopIteration
+            return None
         if not head.startswith(b"FRAME"):
             raise Y4MError("missing FRAME marker")
-        H, W = self.height, self.width
         dt = np.dtype("<u2") if self.hdr else np.dtype(np.uint8)
-        n = H * W * 3 // 2
+        n = self.height * self.width * 3 // 2
         buf = self.f.read(n * dt.itemsize)
         if len(buf) < n * dt.itemsize:
-            raise StopIteration      # trailing partial frame: same policy as the raw reader
-        p = np.frombuffer(buf, dtype=dt)
+            return None              # trailing partial frame: same policy as the raw reader
+        return np.frombuffer(buf, dtype=dt)
+
+    def __next__(self):
+        p = self.read_planar()
+        if p is None:
+            raise StopIteration
+        if self.planar:
+            return p
+        H, W = self.height, self.width
         y = p[:H * W].reshape(H, W)
         u = p[H * W:H * W * 5 // 4].reshape(H // 2, W // 2)
         v = p[H * W * 5 // 4:].reshape(H // 2, W // 2)
@@ -125,6 +137,18 @@ class Y4MWriter:
         cs = "420p10 XYSCSS=420P10" if hdr else "420jpeg"
         toks = [f"W{width}", f"H{height}", f"F{fps_num}:{fps_den}"] + [e for e in extra if not e.startswith("XYSCSS")] + [f"C{cs}"]
         self.f.write(("YUV4MPEG2 " + " ".join(toks) + "\n").encode("ascii"))
+
+    def write_planar(self, frame):
+        """One frame that is planar already (Y, U, V planes of width x height, 10-bit values LSB-aligned), written unconverted."""
+        dt = np.dtype("<u2") if self.hdr else np.dtype(np.uint8)
+        a = np.asarray(frame)
+        if a.dtype != dt:
+            a = a.astype(dt)
+        n = self.height * self.width * 3 // 2
+        if a.size < n:
+            raise Y4MError(f"planar frame has {a.size} elements, need {n}")
+        self.f.write(b"FRAME\n")
+        self.f.write(memoryview(np.ascontiguousarray(a.reshape(-1)[:n])).cast("B"))
 
     def write(self, frame):
         y, u, v = semiplanar_to_planar(frame, self.height, self.width, self.hdr)

@@ -74,6 +74,27 @@ typedef enum hf_output_mode {
 #define HF_FLAG_NO_TIMING 0x200 /* do not record the events behind m_ofcCalcTime / m_warpCalcTime (hf_stats times stay 0).
                                    Every timing event is a barrier packet on the stream: measured 5-6 us each between
                                    back-to-back kernels, ~15 us per source period in a throughput pipeline */
+/* Planar 4:2:0 frames (yuv420p / yuv420p10le, e.g. the frames of a .y4m file or of an ffmpeg rawvideo pipe) instead of NV12 / P010 at
+ * the boundary.  The two flags are independent.  A planar frame of H rows, stride S (input_stride for inputs, output_stride for outputs,
+ * in elements; must be even) and width W holds 1.5 H S elements -- the same bytes as the NV12 / P010 frame, so input_frame_bytes,
+ * output_frame_bytes and every buffer size stay as they are:
+ *     Y(y, x)  at  y S + x                              0 <= y < H,   0 <= x < W
+ *     U(m, k)  at  H S + m (S/2) + k                     0 <= m < H/2, 0 <= k < W/2
+ *     V(m, k)  at  H S + (H/2)(S/2) + m (S/2) + k
+ * In:  NV12.Y(y, x) = Y(y, x), UV(m, 2k) = U(m, k), UV(m, 2k+1) = V(m, k); HDR values are LSB-aligned 10-bit (yuv420p10le) and become
+ *      (v << 6) & 0xFFFF (values above 1023 lose their top bits).  Padding columns [W, S) of a planar input are never read.
+ * Out: the inverse; HDR values become v >> 6 (the low 6 bits of the P010 value are dropped).  Padding columns of a planar output are
+ *      unspecified.
+ * The conversion is a kernel of its own at the boundary (csrc/hf_planar.hip); flow, m_totalFrameDelta, phase planes, diagnostics and timings
+ * are those of the NV12 / P010 path.  Entry points that honour them:
+ *   PLANAR_IN   hf_update_frame, hf_update_frame_device, hf_update_frame_device_ref (converts: no zero-copy reference, see there),
+ *               hf_update_frame_async, the device_frame of hf_interpolate_period(_ex), hf_filter_deliver's host_in, hf_hostio's fill buffers
+ *   PLANAR_OUT  hf_download_frame, hf_download_frame_async, hf_download_frame_device, the device_out of hf_interpolate_period(_ex),
+ *               hf_filter_deliver's host_out, hf_hostio's sink frames; hf_set_output_buffer(ctx, non-NULL) returns HF_ERR_STATE
+ * Contexts with either flag cannot join a batch (hf_batch_create returns HF_ERR_INVALID_ARGUMENT).  Staging buffers are allocated on
+ * first use: up to three frames per side for host I/O, one semi-planar frame per output of hf_interpolate_period. */
+#define HF_FLAG_PLANAR_IN 0x8000
+#define HF_FLAG_PLANAR_OUT 0x10000
 /* (0x10, 0x20, 0x100, 0x400 were round-1 stream-topology experiments -- shared warp stream, priority streams, warp
  *  turnstile, deferred phase planes -- all measured slower or equal; removed, findings in DESIGN.md section 4) */
 
@@ -189,7 +210,8 @@ uint64_t hf_downloads_issued(const hf_ctx* ctx);
 int hf_wait_download(hf_ctx* ctx, uint64_t index);
 /* Zero-copy variant: the ring keeps a REFERENCE to device_frame (e.g. a decoder surface).  The caller must
  * leave the frame untouched until three further frames have been submitted (it stays in the 3-frame ring
- * as frame N, N-1 and N-2, opticalFlowCalcSDR.cpp:22-28). */
+ * as frame N, N-1 and N-2, opticalFlowCalcSDR.cpp:22-28).  Under HF_FLAG_PLANAR_IN the frame is converted into the
+ * context's own ring slot instead: the caller's buffer is free once ctx's stream has passed the call. */
 int hf_update_frame_device_ref(hf_ctx* ctx, const void* device_frame);
 /* One source-frame period in a single call (batch driver): hf_update_frame_device_ref(device_frame) if it is
  * non-NULL, hf_calculate_optical_flow(), then for i < n_out: hf_warp_frames(t[i], mode) written to
@@ -252,7 +274,8 @@ const char* hf_batch_last_error(const hf_batch* batch);   /* batch == NULL: erro
 
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
-/* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer). */
+/* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
+ * write semi-planar frames, so a non-NULL buffer returns HF_ERR_STATE (use hf_download_frame_device). */
 int hf_set_output_buffer(hf_ctx* ctx, void* device_out);
 /* Block until everything enqueued on ctx's stream has finished; finalises timings/total_frame_delta. */
 int hf_sync(hf_ctx* ctx);

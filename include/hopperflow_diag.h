@@ -85,6 +85,12 @@ int hf_hbm_copy_probe(int device_index, size_t bytes, int repeats, double* read_
 int hf_timer_begin(hf_ctx* ctx);
 int hf_timer_end(hf_ctx* ctx, float* elapsed_ms); /* synchronises on the end event */
 
+/* ---- measurement: the planar re-layout kernels of HF_FLAG_PLANAR_IN / _OUT alone (tools/planar_io_rate.py) ----
+ * to_planar = 0: device_src is a planar frame of ctx's input geometry (input_stride), device_dst receives its NV12 / P010 form;
+ * to_planar = 1: device_src is an NV12 / P010 frame of ctx's output geometry (output_stride), device_dst receives its planar form.
+ * Enqueued on ctx's stream (works whatever ctx's flags); blocking contexts wait for it. */
+int hf_planar_convert_device(hf_ctx* ctx, int to_planar, const void* device_src, void* device_dst);
+
 #ifdef __cplusplus
 }
 #endif
