@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- interpolated frames/s (+ ms per flow calc) of the HIP OpticalFlowCalc path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hdr2160_24to120] [--radius 16] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hdr2160_24to120] [--radius 16] [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline and what the timed region
+itself recorded.  Everything that takes runs of its own beside it comes with --full (the entries marked [--full] below; the --no-*
+switches still drop single ones).
 
 A STEP = `--periods-per-step` (64) consecutive source-frame periods for every one of the `--streams` independent
 frame-pair streams a rank owns.  One period of one stream = updateFrame of a device-resident source frame (zero-copy
@@ -19,11 +23,16 @@ One JSON line on rank 0:
                      B_out = 3F + 4N algorithmic bytes per output frame; plus the dominant kernel (the fused period warp)
                      alone on the GPU, priced both with the algorithmic bytes it stands for and with its real HBM traffic
                      (profiles/roofline_traffic.json, generated from rocprofv3 PMC passes by tools/pmc_traffic.py), and its
-                     launch duration inside the timed region (HIP events of the dispatch itself)
-  host_io            the same path with host buffers: pinned asynchronous H2D / D2H on side streams (PCIe-inclusive,
+                     launch duration inside the timed region (HIP events of the dispatch itself); [--full] the same kernel
+                     and the flow chain alone on the GPU (roofline.kernel_isolated, ms_per_flow_calc_isolated*)
+  device             which GPU, clocks and power before and behind the timed region; [--full] an HBM probe of the idle device
+                     and the shader clock under load
+  [--full] host_enqueue_ms_per_step   host cost of a step's calls, from a burst of periods behind the timed region
+  [--full] other_workloads, content   short legs of the other BASELINE configs and content classes (default workload only)
+  [--full] host_io   the same path with host buffers: pinned asynchronous H2D / D2H on side streams (PCIe-inclusive,
                      never `value`)
-  cpu_baseline       the plain-C oracle port on a bounded sample, 1 thread and all host cores
-  reference_opencl   the reference's own OpenCL path (oracle/_ref) on the same GPU when it is available
+  [--full] cpu_baseline       the plain-C oracle port on a bounded sample, 1 thread and all host cores
+  [--full] reference_opencl   the reference's own OpenCL path (oracle/_ref) on the same GPU when it is available
 """
 import argparse
 import json
@@ -71,7 +80,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s mea
 # kernel of their element size and cell width (names as the PMC passes of profiles/roofline_traffic.json saw them dispatched)
 WARP_SYMBOL_PREFIX = {(1, True): "warp_wg_kernel<unsigned short, 2,", (0, False): "warp_fast_kernel<unsigned char, 4, 2, 2, 8, true>",
                       (0, True): "warp_fast_kernel<unsigned char, 8, 2, 2, 16, true>", (1, False): "warp_fast_kernel<unsigned short, 4, 2, 2, 16, true>"}
-# the other BASELINE configs, run as short legs behind the timed region of the default workload (fresh child processes, never `value`)
+# the other BASELINE configs, run with --full as short legs behind the timed region of the default workload (fresh child processes, never `value`)
 OTHER_WORKLOADS = {"sdr1080_24to60": 24, "sdr1080_64pairs": 24, "hdr2160_nb10_blur32": 8, "hdr1080_24to120": 12, "sdr2160_24to60": 8,
                    "sdr360_24to60": 64}   # name: steps (about 1 s timed each); 360p = the size of BASELINE config 1 (the reference's CPU-runnable case)
 # Content classes (hopperrender_amd/synth.py ContentScene; SURVEY.md 8(d) "extra cases"): the reference's cost does not depend on the pixels,
@@ -246,6 +255,9 @@ def parse_args():
                     "steps in the middle of the timed region (hf_batch_timeline_*: no profiler) plus a stand-alone leg of one batch, and write "
                     "the raw records + tools/timeline_report.py's analysis to this JSON file")
     ap.add_argument("--timeline-steps", type=float, default=1.0)
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own beside the headline: the idle-device HBM probe, "
+                    "the shader clock under load, the host-cost burst, the dominant kernel and the flow chain alone, and the host-I/O, CPU, "
+                    "reference and other-workload / content legs (each still subject to its --no-* switch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference", action="store_true")
     ap.add_argument("--no-host-io", action="store_true")
@@ -392,7 +404,7 @@ def other_workloads(a, budget_s=200.0):
     deadline = time.monotonic() + budget_s
     for name, steps in OTHER_WORKLOADS.items():
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", "2", "--radius", str(a.radius),
-               "--no-cpu-baseline", "--no-reference", "--no-host-io", "--no-other-workloads", "--no-content-legs"]
+               "--full", "--no-cpu-baseline", "--no-reference", "--no-host-io", "--no-other-workloads", "--no-content-legs"]
         left = deadline - time.monotonic()
         try:
             if left < 20.0:
@@ -426,7 +438,7 @@ def content_legs(a, budget_s=200.0):
         res[wl] = {}
         for scene in ("bench", "bench_wrap6", "static", "pan64", "chaotic", "cut"):
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--scene", scene.split("_")[0], "--steps", str(steps), "--warmup", "2", "--radius", str(a.radius),
-                   "--content-counters", "--no-cpu-baseline", "--no-reference", "--no-host-io", "--no-other-workloads", "--no-content-legs"]
+                   "--content-counters", "--full", "--no-cpu-baseline", "--no-reference", "--no-host-io", "--no-other-workloads", "--no-content-legs"]
             if scene == "bench_wrap6":
                 cmd += ["--pool-order", "wrap", "--pool", "6"]      # the frame sequence of the bench lines of rounds 1-5
             left = deadline - time.monotonic()
@@ -492,7 +504,7 @@ def main():
 
     import __graft_entry__
     __graft_entry__.build(quiet=True)
-    hbm_idle = hbm_probe(dev_index) if rank == 0 else None     # before any stream of the workload exists
+    hbm_idle = hbm_probe(dev_index) if rank == 0 and a.full else None     # before any stream of the workload exists
     from hopperrender_amd import capi, synth
     from hopperrender_amd.calc import DeviceBuffer, FlowBatch, OpticalFlowCalcHDR, OpticalFlowCalcSDR
     from hopperrender_amd.protocol import SOURCE_24, BlendSchedule
@@ -662,7 +674,7 @@ def main():
     import ctypes as C
     for k in range(a.warmup):
         run_step(k)
-        if rank == 0 and k == a.warmup - 1 and not a.no_clock_probe:
+        if rank == 0 and k == a.warmup - 1 and a.full and not a.no_clock_probe:
             # The shader clock the device sustains under THIS load: a one-wave probe on a stream of its own, 3 ms (the clock moves with the load from millisecond to millisecond), issued behind the last
             # warm-up step while the GPU is still working through it.  NOT inside the timed region: its normal-priority stream only gets
             # through when the highest-priority batch streams leave a gap (measured: the call returns after 0.1-0.7 s), and the issuing
@@ -700,13 +712,16 @@ def main():
         dev_mid.append(device_sample(sysfs))
         if a.dump_outputs:     # before the burst below writes the same output buffers again; every stream follows one schedule
             dump_outputs(a.dump_outputs, calcs, outbufs, schedule[(a.warmup + a.steps) * P - 1], hdr)
-    # What the host loop itself costs: BURST periods issued into EMPTY queues (nothing blocks), per native call
-    tb = time.perf_counter()
-    for i in range((a.warmup + a.steps) * P, (a.warmup + a.steps) * P + BURST):
-        run_period(i)
-    host_call_s = (time.perf_counter() - tb) / BURST     # per source period of all streams of this rank
-    sync_all()
-    host_enqueue_s = host_call_s * P * a.steps
+    # What the host loop itself costs: BURST periods issued into EMPTY queues (nothing blocks), per native call.  The content counters and
+    # the timeline's stand-alone leg below go on from the periods the burst leaves in the rings, so they keep it without --full too.
+    host_enqueue_s = None
+    if a.full or a.content_counters or timeline_on:
+        tb = time.perf_counter()
+        for i in range((a.warmup + a.steps) * P, (a.warmup + a.steps) * P + BURST):
+            run_period(i)
+        host_call_s = (time.perf_counter() - tb) / BURST     # per source period of all streams of this rank
+        sync_all()
+        host_enqueue_s = host_call_s * P * a.steps
 
     content_counters = None
     if a.content_counters and rank == 0 and batches:
@@ -765,7 +780,7 @@ def main():
     # i.e. exactly the launch the pipeline issues (same kernel, same grid), one fused period launch at a time, source frames
     # rotating so that they come from HBM -- and the flow chain of one pair alone.
     isolated = None
-    if rank == 0 and not a.no_profile:
+    if rank == 0 and a.full and not a.no_profile:
         for b in batches:
             b.close()
         batches = []
@@ -814,7 +829,7 @@ def main():
     # one context from pinned host memory and reads every output frame back, all ranks at the same time, each in a child process
     # on its own GPU; rank 0 reports the aggregate.  Never part of `value`.
     host_io_ranks = None
-    if world > 1 and not a.no_host_io:
+    if world > 1 and a.full and not a.no_host_io:
         dist.barrier()
         try:
             mine = host_io_block(hdr, H, W, target, n_periods=24, device=dev_index, async_only=True)
@@ -930,10 +945,10 @@ def main():
             "metric": "interpolated frames/sec + ms/flow-calc, 2160p HDR, 1/2/4/8 MI355X",
             "value": round(value, 1),
             "unit": "frames/s",
-            "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
+            "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup, "full": a.full,
             "ms_per_step": round(1e3 * elapsed_max / a.steps, 4),
             "timed_region_s": round(elapsed_max, 3),
-            "host_enqueue_ms_per_step": round(1e3 * host_enqueue_s / a.steps, 4),
+            "host_enqueue_ms_per_step": round(1e3 * host_enqueue_s / a.steps, 4) if host_enqueue_s is not None else None,
             "host_enqueue_note": f"host time of the calls of one step, measured on a burst of {BURST} periods issued into empty queues behind the "
                                  "timed region; host_issue_wall_ms_per_step is the wall time the issuing loop took INSIDE the timed region, "
                                  "which includes blocking on full hardware queues (back-pressure of the GPU), not host work",
@@ -978,23 +993,23 @@ def main():
                         "streams, every output frame returned to the host (PCIe-inclusive; never the bench `value`)"}
         if content_counters:
             out["content_counters"] = content_counters
-        if world == 1 and a.workload == "hdr2160_24to120" and not a.no_other_workloads:
+        if a.full and world == 1 and a.workload == "hdr2160_24to120" and not a.no_other_workloads:
             out["other_workloads"] = other_workloads(a)
-        if world == 1 and a.workload == "hdr2160_24to120" and a.scene == "bench" and not a.no_content_legs:
+        if a.full and world == 1 and a.workload == "hdr2160_24to120" and a.scene == "bench" and not a.no_content_legs:
             out["content"] = content_legs(a)
-        if not a.no_host_io and world == 1:
+        if a.full and not a.no_host_io and world == 1:
             try:
                 out["host_io"] = host_io_block(hdr, H, W, target)
             except Exception as e:
                 out["host_io"] = {"error": repr(e)}
-        if not a.no_cpu_baseline and world == 1:   # reported baselines: rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # reported baselines: rank 0 at N = 1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(hdr, H, W, target, a.radius, a.neighbor, host_frames, a.cpu_sample_pairs)
                 out["cpu_baseline"]["host_cores_available"] = os.cpu_count()
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(hdr, H, W, target, a.radius, a.neighbor, host_frames)
             except Exception as e:  # the checker must never take the measurement down
                 out["cpu_baseline"] = {"error": repr(e)}
-        if not a.no_reference and world == 1:
+        if a.full and not a.no_reference and world == 1:
             try:
                 r = reference_opencl(hdr, H, W, target, a.radius, a.neighbor, host_frames)
                 if r:

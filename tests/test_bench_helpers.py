@@ -1,5 +1,5 @@
-"""CPU: the parts of bench.py that need no GPU -- the sysfs reader behind the line's `device` block and the writer of
---dump-outputs."""
+"""CPU: the parts of bench.py that need no GPU -- the sysfs reader behind the line's `device` block, the writer of
+--dump-outputs and the --full switch."""
 import os
 import sys
 
@@ -64,3 +64,14 @@ def test_dump_outputs_writes_a_fixed_float_sample_under_64_mb(tmp_path):
     assert fr.shape == (streams, len(ts), len(idx)) and len(np.unique(idx)) == len(idx) and idx.max() < elems
     assert np.array_equal(fr[5, 3], bufs[5][3].download(np.uint16, elems)[idx])
     assert list(a["blend_scalars.npy"]) == ts and list(a["total_frame_delta.npy"]) == [1000 + s for s in range(streams)]
+
+
+def test_full_is_off_unless_asked_for(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` leaves everything beside the headline to --full."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-host-io"])
+    a = bench.parse_args()
+    assert a.full is True and a.no_host_io and (a.steps, a.warmup) == (20, 3)

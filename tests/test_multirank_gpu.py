@@ -66,7 +66,7 @@ def test_named_baseline_configs_4_and_5():
 def test_host_io_leg_at_two_ranks():
     """bench.py at N > 1: every rank runs the asynchronous host-I/O path (pinned buffers, H2D / D2H on side streams) on its
     GPU at the same time and rank 0 reports the aggregate -- the leg SURVEY.md 8(e) names as the expected scaling limit."""
-    two = run_bench([], 2, host_io=True)
+    two = run_bench(["--full"], 2, host_io=True)
     h = two["host_io"]
     assert h["ranks_reporting"] == 2 and not h["errors"]
     assert h["aggregate_frames_per_s"] > 0 and len(h["per_rank_frames_per_s"]) == 2
@@ -88,10 +88,10 @@ def test_eight_ranks_share_config_4_on_one_gpu():
 
 
 def test_default_line_carries_the_other_baseline_configs():
-    """The driver sees ONE bench line: behind the timed region of the default workload bench.py runs ~1 s legs of BASELINE configs 2, 4
-    and 5, of the two sizes round 6 added and of config 1's frame size in child processes and reports them under other_workloads (never
-    part of `value`)."""
-    d = run_bench(["--no-profile"], 1, "hdr2160_24to120")
+    """The driver sees ONE bench line: with --full, behind the timed region of the default workload bench.py runs ~1 s legs of BASELINE
+    configs 2, 4 and 5, of the two sizes round 6 added and of config 1's frame size in child processes and reports them under
+    other_workloads (never part of `value`)."""
+    d = run_bench(["--full", "--no-profile"], 1, "hdr2160_24to120")
     o = dict(d["other_workloads"])
     assert o.pop("failed") == []          # a leg that fails (or does not fit the legs' shared deadline) is named at the top, not hidden in its entry
     assert set(o) == {"sdr1080_24to60", "sdr1080_64pairs", "hdr2160_nb10_blur32", "hdr1080_24to120", "sdr2160_24to60", "sdr360_24to60"}
@@ -129,3 +129,21 @@ def test_default_line_carries_the_other_baseline_configs():
     assert 2000.0 < dev["hbm_streams_idle_device"]["copy_GBps_read_plus_write"] < 8000.0 and dev["hbm_streams_idle_device"]["fill_GBps"] > 2000.0
     for when in ("at_start_of_timed_region", "at_end_of_timed_region"):
         assert dev[when] is None or set(dev[when]) <= {"sclk_mhz", "mclk_mhz", "fclk_mhz", "power_w", "power_cap_w", "temp_c"}
+
+
+def test_plain_run_measures_only_the_headline():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps and the line.  The line keeps the headline
+    and what the timed region itself recorded; what takes runs of its own (legs, baselines, probes, kernels alone) is left to --full."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--periods-per-step", "4"]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u16" and d["ms_per_step"] > 0
+    assert d["ms_per_flow_calc"] > 0 and 0 < d["roofline"]["frac"] < 1 and d["roofline"]["kernel"].startswith("warp_wg_kernel<")
+    for key in ("other_workloads", "content", "host_io", "cpu_baseline", "cpu_baseline_all_cores", "reference_opencl"):
+        assert key not in d, key
+    assert "kernel_isolated" not in d["roofline"] and d["ms_per_flow_calc_isolated"] is None and d["host_enqueue_ms_per_step"] is None
+    assert d["device"]["hbm_streams_idle_device"] is None and d["device"]["shader_clock_mhz_under_load"] is None

@@ -2,7 +2,7 @@
 # tools/r05/baseline.sh -- decomposition of the default pipeline on ONE box: default / eager planes / warps only / chains only,
 # the chain alone (batches of 12 and 16) and the fused period warp alone.
 export TMPDIR=/tmp; O=gpurun_out/r05_base; mkdir -p $O
-Q="--steps 8 --warmup 2 --no-cpu-baseline --no-reference --no-host-io --no-other-workloads"
+Q="--full --steps 8 --warmup 2 --no-cpu-baseline --no-reference --no-host-io --no-other-workloads"
 show() { python3 -c "
 import sys,json
 d=json.loads(open('$1').read().strip().splitlines()[-1]); r=d['roofline']

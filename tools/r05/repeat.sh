@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/r05/repeat.sh -- the same short bench command several times in a row on a fresh box: does the box's state drift?
 export TMPDIR=/tmp
-Q="--steps 10 --no-cpu-baseline --no-reference --no-host-io --no-other-workloads"
+Q="--full --steps 10 --no-cpu-baseline --no-reference --no-host-io --no-other-workloads"
 run() { python bench.py $Q "$@" 2>/dev/null | python3 -c "
 import sys,json,time
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); v=d['device']

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Is the first bench run on a box slower, for how long, and does an idle pause bring the state back?  (2160p HDR default workload, short runs)
-Q="--no-cpu-baseline --no-reference --no-host-io --no-other-workloads --no-content-legs --no-clock-probe"
+Q="--full --no-cpu-baseline --no-reference --no-host-io --no-other-workloads --no-content-legs --no-clock-probe"
 run() { python bench.py $Q "$@" 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); dv=d['device']
