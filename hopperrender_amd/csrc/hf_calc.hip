@@ -54,6 +54,7 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
         hf::launch_flow_big_argmin(g, b, s);
     };
     const bool lazy = !(c->cfg.flags & HF_FLAG_NO_LAZY_ARGMIN);
+    bool tables_fresh = false;                                    // the previous level of THIS chain refreshed the SAD tables
     for (int k = 0; k < iters; k++) {                             // window halves every level (:110)
         const bool use_neighbors = k >= 4;                        // calcDeltaSumsKernelSDR.h:3,112
         if (use_neighbors) flush_pending();                       // a launch with a neighbour term reads other windows' entries
@@ -77,6 +78,11 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
                 if (!small) f.sums = m->sums + (size_t)step_index * m->sums_stride;
                 pending[i] = hf::PendingArgmin{};
             }
+            // sad_read follows from the previous level's window size; what makes it right is that that level wrote the tables (windows 32 .. 4
+            // do, 2 does not: true while the window halves at every level and the chain ends at 2)
+            if (a.s[0].sad_read && !tables_fresh)
+                return fail(c, HF_ERR_STATE, "flow chain: level %d (window %d) would read SAD tables that level %d did not write", k, c->levels[k].window, k - 1);
+            tables_fresh = a.s[0].sad_write != 0;
             if (small) {
                 hf::launch_flow_level_small(g, a, s);
             } else {

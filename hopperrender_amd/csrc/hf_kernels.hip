@@ -169,8 +169,10 @@ __global__ __launch_bounds__(256) void blur_flow_kernel(const BlurBatch batch, i
         for (int i = tid; i < NW * NW; i += 256) {
             const int j = i / NW, k = i - j * NW;
             int wa = wa0 + k, wb = wb0 + j;
-            wa = wa < 0 ? -1 - wa : wa >= L.nwx ? 2 * L.nwx - 1 - wa : wa;
-            wb = wb < 0 ? -1 - wb : wb >= L.nwy ? 2 * L.nwy - 1 - wb : wb;
+            // one reflection, then the clamp of mirror_flow: with r / 2 + 16 > nw a tile's surplus windows (they feed only outputs outside the
+            // grid) reflect past the other edge -- lh = 66, r = 64: wb = -14
+            wa = clampi(wa < 0 ? -1 - wa : wa >= L.nwx ? 2 * L.nwx - 1 - wa : wa, 0, L.nwx - 1);
+            wb = clampi(wb < 0 ? -1 - wb : wb >= L.nwy ? 2 * L.nwy - 1 - wb : wb, 0, L.nwy - 1);
             const int w = wb * L.nwx + wa;
             HF_DBG_CHECK(wb >= 0 && wb < L.nwy && wa >= 0 && wa < L.nwx, 201);
             v[i] = (uint32_t)(uint16_t)L.tx[w] | ((uint32_t)(uint16_t)L.ty[w] << 16);

@@ -6,7 +6,8 @@ reflection of calcDeltaSumsKernelSDR.h:86-95, which the HIP path clamps).
   * the self-test proves the checker fires: 64 out-of-range indices issued, 64 recorded, site 999;
   * a subset of the parity suite runs under the checking library in a child process (HF_LIB) -- tiny frames with huge offsets (the
     reference-UB case), ragged and strided sizes, the staged period warp with injected extreme flows at 2160p HDR, a batched
-    chain -- and must finish with ZERO recorded violations and unchanged results (the tests' own assertions)."""
+    chain, the window-sum blur on grids smaller than a tile's gather, two batched chains of tests/test_chain_variants_gpu.py -- and must
+    finish with ZERO recorded violations and unchanged results (the tests' own assertions)."""
 import os
 import subprocess
 import sys
@@ -101,6 +102,25 @@ for k in range(3):
 batch.sync()
 assert violations(ms[0])[0] == 0, violations(ms[0])
 batch.close()
+for m in ms: m.close()
+for row in outs:
+    for o in row: o.free()
+for d in dev: d.free()
+
+# 6. the window-sum blur where a tile gathers more windows than the grid has (sites 201 / 215: small even grids, large even radii), single
+#    and batched, and two batched chains of the variant matrix: HDR 240 x 136 with five members and tables, rs 1 with four
+import chain_variant_model as M
+import test_chain_variants_gpu as V
+probe = OpticalFlowCalcSDR(64, 96)
+for lw, lh in V.SMALL_GRIDS:
+    for r in (38, 48, 64):
+        for n in (1, 5):
+            V.run_small_grid_blur(lw, lh, r, n)
+            assert violations(probe)[0] == 0, (lw, lh, r, n, violations(probe))
+for name in ("hdr1088-n5-tab", "sdr540-n4-tab"):
+    V.run_case(M.case(name))
+    assert violations(probe)[0] == 0, (name, violations(probe))
+probe.close()
 print("DEBUG-BOUNDS-OK")
 """
 

@@ -6,39 +6,19 @@ and against the same library with HF_FLAG_NO_SAD_REUSE, on inputs where the deci
   * grids with partial tiles (their windows never touch the tables), a 240-wide grid whose last 16 columns are a full 16-wide tile of the
     row-per-lane level-2 mapping inside a partial 32 x 32 tile, grids whose first small level is 16 (no level before it to reuse);
   * R = 5 (no full tiles at all), other delta / neighbour scalars, fewer iterations;
-  * batches of 2 (a row per lane at the two finest levels) and of 6 (a block per lane).
+  * batches of 2 (a row per lane at the two finest levels) and of 6 (a block per lane) at 1080p SDR; the kernel variants that the batch size,
+    the resolution scalar, the radius and the table mode select are held to the oracle one by one in tests/test_chain_variants_gpu.py.
 Bar: bit-exact offsets, blurred flow and total frame delta (calcDeltaSumsKernelSDR.h:61-190, determineLowestLayerKernelSDR.h:16-26,
 adjustOffsetArrayKernelSDR.h:11-19, opticalFlowCalcSDR.cpp:68-111)."""
-import numpy as np
+import os
+import sys
+
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from chain_content import frames as _frames  # noqa: E402  (shared with test_chain_variants_gpu.py)
+
 pytestmark = pytest.mark.gpu
-
-
-def _patched(frame_a, H, S, hdr, seed, n=40):
-    """frame_a with n rectangular patches (8 .. 96 px) of fresh noise: the rest of the frame is static."""
-    rng = np.random.default_rng(seed)
-    f = frame_a.copy()
-    y = f[:H * S].reshape(H, S)
-    uv = f[H * S:].reshape(H // 2, S)
-    hi = 65536 if hdr else 256
-    for _ in range(n):
-        ph, pw = int(rng.integers(4, min(49, H // 4))) * 2, int(rng.integers(4, min(49, S // 4))) * 2
-        y0, x0 = int(rng.integers(0, (H - ph) // 2)) * 2, int(rng.integers(0, (S - pw) // 2)) * 2
-        y[y0:y0 + ph, x0:x0 + pw] = rng.integers(0, hi, size=(ph, pw))
-        uv[y0 // 2:(y0 + ph) // 2, x0:x0 + pw] = rng.integers(0, hi, size=(ph // 2, pw))
-    return f
-
-
-def _frames(kind, H, W, hdr, seed):
-    from hopperrender_amd import synth
-    if kind == "patches":
-        a = synth.Scene(H, W, hdr, seed=seed).frame(0)
-        return [a, a, _patched(a, H, W, hdr, seed + 1)]
-    if kind == "noise":
-        return [synth.random_frame(H, W, hdr, seed=seed + i) for i in range(3)]
-    sc = synth.ContentScene(kind, H, W, hdr, seed)
-    return [sc.frame(i) for i in range(3)]
 
 
 def _run(cls, H, W, max_res, f, R=16, delta=8, nb=6, iterations=0, flags=None):
