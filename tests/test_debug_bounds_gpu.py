@@ -6,7 +6,8 @@ reflection of calcDeltaSumsKernelSDR.h:86-95, which the HIP path clamps).
   * the self-test proves the checker fires: 64 out-of-range indices issued, 64 recorded, site 999;
   * a subset of the parity suite runs under the checking library in a child process (HF_LIB) -- tiny frames with huge offsets (the
     reference-UB case), ragged and strided sizes, the staged period warp with injected extreme flows at 2160p HDR, a batched
-    chain, the window-sum blur on grids smaller than a tile's gather, two batched chains of tests/test_chain_variants_gpu.py -- and must
+    chain, the window-sum blur on grids smaller than a tile's gather, two batched chains of tests/test_chain_variants_gpu.py, three staged
+    warp cases of tests/test_warp_variants_gpu.py (a deep edge window, unsigned char at rs 4, a cell taller than the tile) -- and must
     finish with ZERO recorded violations and unchanged results (the tests' own assertions)."""
 import os
 import subprocess
@@ -119,6 +120,14 @@ for lw, lh in V.SMALL_GRIDS:
             assert violations(probe)[0] == 0, (lw, lh, r, n, violations(probe))
 for name in ("hdr1088-n5-tab", "sdr540-n4-tab"):
     V.run_case(M.case(name))
+    assert violations(probe)[0] == 0, (name, violations(probe))
+# 7. the staged period warp's own sites (10 .. 14, 210 .. 213) in three cases of tests/test_warp_variants_gpu.py: edge windows that reach 60
+#    elements into the mirror zone, unsigned char at rs 4, flow cells taller than the workgroup tile (rs 6)
+import warp_variant_model as WM
+import test_warp_variants_gpu as WV
+for name in ("staged-u16-res136-deep-n14", "staged-u8-res68-n15", "staged-u16-res17-n14"):
+    assert any(ln.staged for ln in WM.launches(WM.case(name), 2)), name
+    WV.run_case(WM.case(name))
     assert violations(probe)[0] == 0, (name, violations(probe))
 probe.close()
 print("DEBUG-BOUNDS-OK")

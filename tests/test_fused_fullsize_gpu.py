@@ -10,10 +10,14 @@ that path only inside a batch of >= 11 members (a single context produces one ou
 and compare every output frame whose blending scalar the golden file covers by SHA-256 with the reference's frame
 (reference warpFrameKernel{SDR,HDR}.h:116-184 run through oracle/_ref on an MI355X), every other one with the oracle
 evaluated on the reference's own blurred flow."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from helpers import Golden, sha
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import Golden, sha  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -231,6 +235,11 @@ def test_staged_warp_and_its_fallbacks_match_oracle_and_global_path(native_lib, 
     outs_b = [[DeviceBuffer(single.output_frame_bytes) for _ in ts] for _ in range(n)]
     batch = FlowBatch(members)
     plans = [ts[i:] + ts[:i] for i in range(n)]
+    # which body every workgroup takes: the CPU model of warp_wg_body (tests/warp_variant_model.py), all members together
+    import warp_variant_model as M
+    mg = M.geometry(M._c(flow_kind, 1, H, W, 270, n))
+    members[0].countersEnable(True)
+    seen = [0, 0, 0]
     for mode in (2, 0, 1):
         single.interpolateOnly(ts, [b.ptr for b in outs_s], mode)
         single.sync()
@@ -243,6 +252,18 @@ def test_staged_warp_and_its_fallbacks_match_oracle_and_global_path(native_lib, 
             m.sync()
             for j, t in enumerate(plans[i]):
                 assert np.array_equal(outs_b[i][j].download(np.uint16), want[t]), (flow_kind, mode, i, t)
+        wg = members[0].counters(reset=True)["warp_workgroups"]
+        model = [sum(v) for v in zip(*(M.wg_member(mg, flow, plans[i], mode)[1] for i in range(n)))]
+        assert [wg["staged"], wg["interior_global"], wg["generic"]] == model and sum(model) == n * 3060, (flow_kind, mode, wg, model)
+        seen = [a + b for a, b in zip(seen, model)]
+    # ... and the kind forces what its name says
+    share = [v / sum(seen) for v in seen]
+    if flow_kind == "uniform_small":
+        assert share[0] > 0.98 and seen[1] == 0, seen
+    elif flow_kind in ("uniform_large", "vertical_fast"):
+        assert share[1] > 0.5 and seen[2] > 0, seen
+    elif flow_kind == "half_and_half":
+        assert min(share) > 0.1, seen
     batch.close()
     for c in [single] + members:
         c.close()
