@@ -67,10 +67,9 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
                 f.prev = k ? m->levels[k - 1] : none;             // :68-69: the chain starts from zero offsets
                 f.prev2 = k > 1 ? m->levels[k - 2] : none;
                 f.level_index = k;
-                // SAD tables: written by every small level that has a successor's worth of blocks (windows 32 .. 4), read by every small
-                // level behind a small level
-                f.sad_write = c->tab_mode && m->sadtab && small && m->levels[k].window >= 4;
-                f.sad_read = c->tab_mode && m->sadtab && small && k > 0 && m->levels[k - 1].window <= 32;
+                // SAD tables: which levels write and read them is hf_launch_plan.h's
+                const hf::SadUse sad = hf::plan_sad_tables(m->levels.data(), k, c->tab_mode && m->sadtab);
+                f.sad_write = sad.write; f.sad_read = sad.read;
                 f.use_neighbors = use_neighbors;
                 f.axis = axis;
                 f.capture_delta = (k == 0 && axis == 0);          // :91

@@ -1439,18 +1439,6 @@ __global__ void expand_offsets_kernel(const Geom g, const FlowLevel L, int16_t* 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-PhaseLayout make_phase_layout(const Geom& g, int max_iterations) {
-    PhaseLayout pl{};
-    pl.rs = g.rs;
-    pl.nph = 1 << g.rs;
-    pl.nph2 = pl.nph > 1 ? pl.nph / 2 : 1;
-    const int reach = (max_iterations + 1) * 64 + 8;   // |offset| <= iterations * (R/2)^2, + one candidate, R <= 16
-    pl.mx = (((reach >> g.rs) + 2 + 3) / 4) * 4;        // multiple of 4: margin groups line up with the 4-column groups
-    pl.lwp = ((g.lw + 2 * pl.mx + 4 + 31) / 32) * 32;   // a strip may start at column lw + mx; rows start on a 128-byte line
-    pl.bytes = (size_t)g.H * pl.nph2 * pl.lwp * sizeof(uint32_t);
-    return pl;
-}
-
 template <typename E>
 static bool launch_prep_fast(const Geom& g, const PhaseLayout& pl, const PrepBatch& b, hipStream_t stream) {
     const int lw = g.W >> g.rs;
@@ -1508,69 +1496,55 @@ void launch_prep_frame(const Geom& g, const PhaseLayout& pl, const void* frame, 
     launch_prep_frames(g, pl, b, stream);
 }
 
-// Batches up to this size run the two finest levels with one row per lane (MapRow).  Chain alone, us per batched chain with a block /
-// a row per lane: 1 pair 79.5 / 71.3, 2 pairs 94.6 / 86.8, 4 pairs 122.4 / 119.2, 8 pairs 169.3 / 173.8.
-constexpr int kRowPerLaneMaxBatch = 4;
-#ifndef HF_LEVEL32_ONE_WAVE_MIN_BATCH
-#define HF_LEVEL32_ONE_WAVE_MIN_BATCH 4
-#endif
-constexpr int kLevel32OneWaveMinBatch = HF_LEVEL32_ONE_WAVE_MIN_BATCH;   // batches from this size on: level 32 as one wave per window
+// The plan's tile shapes (hf_launch_plan.h) are the device maps'.
+static_assert(plan_flow_level_small(1, 2, 16, false, false, false).tile_w == MapRow<2>::TW && plan_flow_level_small(1, 2, 16, false, false, false).waves == MapRow<2>::WAVES &&
+              plan_flow_level_small(1, 4, 16, false, false, false).waves == MapRow<4>::WAVES && MapRow<4>::TW == 32, "row-per-lane tiles");
+static_assert(plan_flow_level_small(32, 2, 16, false, false, false).waves == Map<2>::WAVES && plan_flow_level_small(32, 4, 16, false, false, false).waves == Map<4>::WAVES &&
+              plan_flow_level_small(32, 8, 16, false, false, false).waves == Map<8>::WAVES && plan_flow_level_small(32, 16, 16, false, false, false).waves == Map<16>::WAVES &&
+              Map<2>::TW == 32 && Map<4>::TW == 32 && Map<8>::TW == 32 && Map<16>::TW == 32 && Map<32>::TW == 32, "block-per-lane tiles");
+
 void launch_flow_level_small(const Geom& g, const FlowBatch& b, hipStream_t stream) {
     const int ws = b.s[0].cur.window;
-    const bool rows1 = b.n <= kRowPerLaneMaxBatch && ws <= 4;
-    const int tw = rows1 && ws == 2 ? MapRow<2>::TW : 32;
-    const int tiles_x = (g.lw + tw - 1) / tw, tiles_y = (g.lh + 31) / 32;   // (32 x 32 tiles at every level but MapRow<2>: 16 x 32)
+    const SmallLevelPlan P = plan_flow_level_small(b.n, ws, b.s[0].R, b.s[0].sadtab != nullptr, b.s[0].sad_read != 0, b.s[0].sad_write != 0);
+    const int tiles_x = (g.lw + P.tile_w - 1) / P.tile_w, tiles_y = (g.lh + 31) / 32;
     FlowBatchArgs kb = pack_batch(b, tiles_x, tiles_y);
     // dynamic LDS: the candidate rows of the Y step (full tiles only exist at the full search radius)
-    const size_t lds = b.s[0].R != 16 ? 0 : ws == 32 ? ystage_bytes<32, 8, 4>(g.rs) : ws == 16 ? ystage_bytes<16, 4, 1>(g.rs) : ws == 8 ? win8_stage_bytes(g.rs) : 0;
-    // windows <= 16 never span waves: one-wave workgroups (SPLIT), see flow_level_small_kernel
-    const dim3 grd(xcd_grid(tiles_x, tiles_y, 1, b.n));
-    auto split = [&](int waves) { return dim3(xcd_grid(tiles_x, tiles_y, waves, b.n)); };
+    const size_t lds = b.s[0].R != 16 ? 0 : P.one_wave32 ? ystage_bytes<32, 8, 1>(g.rs) : ws == 32 ? ystage_bytes<32, 8, 4>(g.rs) : ws == 16 ? ystage_bytes<16, 4, 1>(g.rs) :
+                       ws == 8 ? win8_stage_bytes(g.rs) : 0;
+    const dim3 grd(xcd_grid(tiles_x, tiles_y, P.waves, b.n)), blk(P.block);
     kb.common.y_rows_lds = lds != 0;
-    const bool tabk = b.s[0].sadtab && b.s[0].R == 16 && (b.s[0].sad_read || b.s[0].sad_write);
-#define HF_LEVEL(NAME, WS_, SPLIT_, ROWS1_, GRID, BLOCK, LDS)                                                                            \
+#define HF_LEVEL(NAME, WS_, SPLIT_, ROWS1_)                                                                                              \
     do {                                                                                                                                 \
-        if (tabk) HF_LAUNCH(NAME, (flow_level_small_kernel<WS_, SPLIT_, ROWS1_, true>), GRID, BLOCK, LDS, stream, g, kb);                \
-        else HF_LAUNCH(NAME, (flow_level_small_kernel<WS_, SPLIT_, ROWS1_, false>), GRID, BLOCK, LDS, stream, g, kb);                    \
+        if (P.tabk) HF_LAUNCH(NAME, (flow_level_small_kernel<WS_, SPLIT_, ROWS1_, true>), grd, blk, lds, stream, g, kb);                 \
+        else HF_LAUNCH(NAME, (flow_level_small_kernel<WS_, SPLIT_, ROWS1_, false>), grd, blk, lds, stream, g, kb);                       \
     } while (0)
     switch (ws) {
         case 32:
-            if (b.n >= kLevel32OneWaveMinBatch) {      // one wave per window (flow_level32_wave_kernel)
-                const size_t lds1 = b.s[0].R != 16 ? 0 : ystage_bytes<32, 8, 1>(g.rs);
-                kb.common.y_rows_lds = lds1 != 0;
-                if (tabk) HF_LAUNCH("level_32", (flow_level32_wave_kernel<true>), grd, dim3(64), lds1, stream, g, kb);
-                else HF_LAUNCH("level_32", (flow_level32_wave_kernel<false>), grd, dim3(64), lds1, stream, g, kb);
+            if (P.one_wave32) {      // one wave per window (flow_level32_wave_kernel)
+                if (P.tabk) HF_LAUNCH("level_32", (flow_level32_wave_kernel<true>), grd, blk, lds, stream, g, kb);
+                else HF_LAUNCH("level_32", (flow_level32_wave_kernel<false>), grd, blk, lds, stream, g, kb);
                 break;
             }
-            HF_LEVEL("level_32", 32, false, false, grd, dim3(256), lds);
+            HF_LEVEL("level_32", 32, false, false);
             break;
-        case 16: HF_LEVEL("level_16", 16, true, false, split(Map<16>::WAVES), dim3(64), lds); break;
-        case 8: HF_LEVEL("level_8", 8, true, false, split(Map<8>::WAVES), dim3(64), lds); break;
+        case 16: HF_LEVEL("level_16", 16, true, false); break;
+        case 8: HF_LEVEL("level_8", 8, true, false); break;
         case 4:
-            if (rows1) HF_LEVEL("level_4", 4, true, true, split(MapRow<4>::WAVES), dim3(64), 0);
-            else HF_LEVEL("level_4", 4, true, false, split(Map<4>::WAVES), dim3(64), 0);
+            if (P.rows1) HF_LEVEL("level_4", 4, true, true);
+            else HF_LEVEL("level_4", 4, true, false);
             break;
         default:
-            if (rows1) HF_LEVEL("level_2", 2, true, true, split(MapRow<2>::WAVES), dim3(64), 0);
-            else HF_LEVEL("level_2", 2, true, false, split(Map<2>::WAVES), dim3(64), 0);
+            if (P.rows1) HF_LEVEL("level_2", 2, true, true);
+            else HF_LEVEL("level_2", 2, true, false);
             break;
     }
 #undef HF_LEVEL
 }
 
-// Waves per workgroup.  A chain alone (2160p HDR, 16 pairs): 4 waves 214 us, 1 wave 224 us (more atomics, and the Y launch's candidate rows
-// come out of L2 instead of LDS).  Inside a throughput pipeline the other queues' kernels hold most of every CU and a single wave finds
-// room sooner: same-box A-B with one-wave workgroups 1080p SDR + 1.4-3 %, 2160p SDR + 2.5 %, 64 pairs + 0.9 %, 1080p HDR + 0.3 %, 2160p HDR
-// (bandwidth-bound) +- 0; 360p (rs = 1) - 1.5 %.  A throughput driver's batches at rs >= 2 take one wave.  (Measured, round 6; before level 32
-// became a one-wave launch too, 2160p HDR lost 2 % with them; a 16 x 16 one-wave Y tile with staged rows was no better than the plain one.)
-#ifndef HF_BIG_ONE_WAVE_MIN_BATCH
-#define HF_BIG_ONE_WAVE_MIN_BATCH 4
-#endif
-constexpr int kBigWavesPerBlock = 4, kBigOneWaveMinBatch = HF_BIG_ONE_WAVE_MIN_BATCH, kBigOneWaveMinRs = 2;
 void launch_flow_big_partial(const Geom& g, const FlowBatch& b, hipStream_t stream) {
     const bool y = b.s[0].axis == 1;
     const char* name = y ? "large_windows_y" : "large_windows_x";
-    const int wpb = b.n >= kBigOneWaveMinBatch && g.rs >= kBigOneWaveMinRs ? 1 : kBigWavesPerBlock;
+    const int wpb = plan_flow_big_waves(b.n, g.rs);
     const int tiles_x = (g.lw + 63) / 64, tiles_y = (g.lh + 4 * wpb - 1) / (4 * wpb);
     const dim3 grd(xcd_grid(tiles_x, tiles_y, 1, b.n));
     const size_t lds = y && b.s[0].R == 16 && wpb == 4 ? ystage_bytes<16, 16, 4>(g.rs) : 0;   // Y launches: candidate rows

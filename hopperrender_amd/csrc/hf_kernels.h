@@ -9,6 +9,7 @@
 #include <hip/hip_ext.h>
 #endif
 #include <stdint.h>
+#include "hf_launch_plan.h"   // Geom, PhaseLayout, FlowLevel, WarpPeriod, FastDiv, the launch constants and plan functions (host-only)
 
 // Device debug build (`python -m hopperrender_amd.build --debug-bounds` => -DHF_DEBUG_BOUNDS, library libhopperflow_dbg.so): every
 // gather index of the kernels (frame / phase-plane / flow-table / LDS-window reads) is checked against its buffer; a violation is
@@ -60,26 +61,7 @@ extern thread_local LaunchObserver* t_launch_observer;
     } while (0)
 #endif
 
-// Geometry shared by all kernels (reference ctor, opticalFlowCalcSDR.cpp:206-222).
-struct Geom {
-    int hdr;             // 0: uint8 elements, 1: uint16 elements
-    int H, W;            // full-resolution luma size
-    int in_stride;       // elements
-    int out_stride;      // elements
-    int rs;              // resolution scalar
-    int lw, lh;          // low-res grid
-};
-
-// Division of a wave-uniform index by a launch constant on the SCALAR unit: u / d == mulhi(u, ceil(2^32 / d)) while u * d < 2^32.
-// Left to the compiler a uniform u / d is ~25 VECTOR instructions (v_rcp_iflag_f32, v_mul_hi_u32 ...) and every workgroup of the
-// batched kernels decodes its unit index with three of them before it can start.  Every launcher builds its dividers with the largest
-// index the launch decodes (make_fastdiv(d, max_u)): where the multiply-high form would not be exact -- grids far beyond 8K -- the
-// divider carries magic == 0 and the kernel takes the plain division (a uniform branch; tests/test_fastdiv_math.py).
-struct FastDiv { uint32_t d, magic; };
-inline bool fastdiv_exact(uint64_t max_u, uint32_t d) { return max_u * d < (1ull << 32); }
-inline FastDiv make_fastdiv(uint32_t d, uint64_t max_u) {
-    return FastDiv{d, d > 1 && fastdiv_exact(max_u, d) ? (uint32_t)(((1ull << 32) + d - 1) / d) : 0u};
-}
+// The device half of FastDiv (hf_launch_plan.h).
 #ifdef __HIPCC__
 __device__ __forceinline__ uint32_t fastdiv(uint32_t u, const FastDiv f) { return f.magic ? __umulhi(u, f.magic) : f.d > 1 ? u / f.d : u; }
 #endif
@@ -88,34 +70,6 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t u, const FastDiv f) { retur
 //   [0 .. 2]                       period-warp workgroups by path: staged window, interior-global, generic (warp_wg_kernel)
 //   [8 + 4 k + 2 axis + {0, 1}]    level k of the chain: windows of its table tiles, those of them that reused their SAD vectors
 constexpr int kCounterWarp = 0, kCounterLevels = 8, kCounterWords = 8 + 4 * 16;
-constexpr int kMaxFlowBatch = 32;      // contexts per hf_batch (FlowBatch below)
-constexpr int kMaxWarpBatch = 16;      // members per fused warp launch (its per-member arguments are 168 bytes; a launch carries 4 KB)
-constexpr int kMaxWarpOutputs = 6;     // outputs of one source period at 24 -> 120 fps (HopperRender.cpp:944-948)
-
-// Phase-plane layout of a frame (hf_flow.hip).  ONE plane of 4-byte elements, one element per grid column, per pair of
-// luma phases and per full-resolution luma row:
-//     PP[y][ph2][j] = Y[y][x] | Y[y][x + 1] << 8 | U[y >> 1][x & ~1] << 16 | V[y >> 1][x & ~1] << 24      (top 8 bits each)
-//     x = (j << rs) + 2 * ph2, mirrored once at the frame edge; j in [-mx, lwp - mx).
-// A candidate sample of `PX` consecutive grid pixels is PX consecutive elements: one DWORD-ALIGNED 16-byte load (luma and
-// chroma together), whatever the candidate offset is.  (Round 1 kept byte planes for luma and 2-byte planes for chroma:
-// their 4- and 8-byte strips started at arbitrary byte offsets, and a vector load that is not dword-aligned takes a 3-4x
-// slower path through the texture addresser -- the chain kernels ran at 78 % TA busy.)
-struct PhaseLayout {
-    int rs, nph, nph2;       // 2^rs luma phases, max(1, nph/2) phase pairs
-    int mx;                  // left margin in grid units (covers every reachable offset, reflection baked in)
-    int lwp;                 // row pitch in elements (multiple of 4)
-    size_t bytes;            // H * nph2 * lwp * 4
-};
-PhaseLayout make_phase_layout(const Geom& g, int max_iterations);
-
-// Offsets of one refinement level: one (x, y) pair per window of size `window`.
-struct FlowLevel {
-    int window, log2w;       // window size (power of two >= 2)
-    int nwx, nwy;            // windows per grid row / column
-    int16_t* tx;             // [nwy][nwx] X offsets after this level (nullptr: level does not exist = all zero)
-    int16_t* ty;             // [nwy][nwx] Y offsets after this level
-};
-
 // A large-window step whose argmin has not been taken yet: the NEXT launch resolves it in its prologue
 // (every workgroup recomputes the 16-way argmin of the window it lies in; the workgroup at the window's
 // origin also stores the result in the level table) instead of a separate tiny launch.  Only used for
@@ -210,26 +164,13 @@ void launch_pack_flow(const Geom& g, const int16_t* flow, uint32_t* packed, hipS
 // All outputs of one source period in ONE launch (fast path only: modes 0-2 etc.), for up to kMaxFlowBatch contexts of
 // the same geometry at once; returns false when the shape of a member does not qualify and the caller must fall back to
 // one launch_warp per output.
-struct WarpPeriod {
-    const void* frame12;
-    const void* frame21;
-    const int16_t* flow;
-    const uint32_t* flow_xy;
-    int n_out;
-    void* outs[kMaxWarpOutputs];
-    float ts[kMaxWarpOutputs];
-    float black, white;      // already scaled for HDR
-    uint32_t* plane21 = nullptr;   // deferred phase plane: build the full plane of frame21 here if the launch can (see below)
-    uint32_t* counters = nullptr;  // diagnostic counters of the launch (member 0's are used), nullptr: none
-};
 // pl + planes_built[n] (optional): members whose period carries a plane21 pointer get the full phase plane of their frame21 built
 // by the launch itself when it is the workgroup-staged kernel and geometry / alignment allow (planes_built[m] says so); everyone
 // else's plane stays untouched and has to be built by launch_prep_frames.
 bool launch_warp_periods(const Geom& g, int n, const WarpPeriod* periods, int mode, hipStream_t stream,
                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const PhaseLayout* pl = nullptr,
                          bool* planes_built = nullptr);
-// Static part of that decision for a batch of n_members contexts of geometry g (hf_batch decides once whether it defers its planes).
-bool warp_period_can_build_planes(const Geom& g, const PhaseLayout& pl, int n_members);
+// (warp_period_can_build_planes, the static part of that decision which hf_batch takes once, is in hf_launch_plan.h.)
 // warpFrameKernel, both planes in one launch.  black/white already scaled for HDR.
 void launch_warp(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
                  void* out, float t, int mode, float black, float white, hipStream_t stream,

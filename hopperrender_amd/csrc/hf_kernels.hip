@@ -937,21 +937,8 @@ __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a,
 // Thread = VEC consecutive elements x ROWS consecutive rows that share one flow-cell row (ROWS
 // divides 2^rs).  Flow lookups and displacement maths are done once per GROUP and reused for the
 // ROWS rows; all 2 * ROWS source runs are requested before any is consumed.
-// Waves (= consecutive wave tiles of a tile row) per workgroup, chosen per launch: 4, or 16 for the batched periods of large
-// frames.  Measured on MI355X, 2160p HDR pipeline (32 pair streams = 2 batches of 16), k frames/s: 67.0 / 67.6 / 68.9 / 68.7 /
-// 67.8 / 68.8 / 70.0 with 4 / 5 / 6 / 8 / 10 / 15 / 16 waves (+2.6 % with one batch stream); a single period is 46 us with 4
-// and 52 us with 16 (760 workgroups for 256 CUs), and the short one-output waves of frames up to 1080p lose 8 % with 16.
-constexpr int kWarpWavesSmall = 4, kWarpWavesLarge = 16;
-// (only the one-flow-cell-per-thread instances are compiled for 1,024-thread workgroups = at most 128 VGPRs: the others need more)
-constexpr int warp_max_waves(size_t elem, int group, int vb) { return vb == 16 && group * (int)elem == 16 ? kWarpWavesLarge : kWarpWavesSmall; }
-// VB = bytes of output per thread and row: 16, or 8 for small frames (<= 1080p 8-bit), where 16-byte threads
-// leave too few waves to hide the per-wave latency chain (one round of fat waves: 9.4 us for 9.3 MB).
-// Wave tile = kWarpTX lanes x kWarpTY row groups: (16 x VEC) elements wide, (4 x ROWS) rows high -- at 2160p HDR 128 pixels
-// x 8 rows = 16 flow cells of one cell row.  (Round 1 used 64 lanes along x: 7.5 tiles per 3840-pixel row, of which the
-// first and the last contain lanes whose runs reach into the mirror zone of warpFrameKernelSDR.h:12-20, so 27 % of all
-// waves executed the per-element edge path next to the run path -- that, not the interior code, was most of the
-// 1,940 VALU instructions per wave.  With 128-pixel tiles 2 of 30 tiles per row are edge tiles.)
-constexpr int kWarpTX = 16, kWarpTY = 4;
+// Waves per workgroup (4 or 16, chosen per launch), VB = bytes of output per thread and row (16, or 8 for small frames) and the wave tile of
+// kWarpTX lanes x kWarpTY row groups: hf_launch_plan.h, with the measurements behind them.
 constexpr int ilog2c(int v) { return v <= 1 ? 0 : 1 + ilog2c(v >> 1); }
 // Deferred phase planes (see warp_wg_kernel): plane-building workgroups carried by a period warp launch.
 struct PlaneOut {
@@ -1014,16 +1001,7 @@ __global__ __launch_bounds__(64 * warp_max_waves(sizeof(E), GROUP, VB)) void war
 // (per wave: 1.55 x).  The window is found per workgroup (per-wave min / max over lanes and outputs of the runs' 16-byte chunks
 // and rows -- packed 16-bit DPP butterfly -- combined through LDS); workgroups whose runs do not fit the LDS budget (fast or
 // diverging motion), touch the mirror zone or contain a partial wave take the global path (warp_fast_body): same results.
-// Shape of the staged kernel (all measured on the 2160p HDR pipeline, 2 batch streams of 16, k frames/s -- DESIGN.md appendix C):
-//   waves (= vertically stacked wave tiles) per workgroup: 68.8-70.0 without staging, 71.9-72.5 / 72.9-73.4 / 73.9-74.1 / 66.7-67.8 / 61.3
-//   with 2 / 3 / 4 / 6 / 16 waves;  rows per thread: 2 (4 rows = half the waves: alone 672 vs 663 us per 16 members, pipeline 69.4 vs
-//   72.4: the other stream's chain waits longer for the fewer, longer waves);  window budget 160 / 176 / 192 / 224 / 256 chunks per wave:
-//   192 best (smaller: more fallbacks; larger: one workgroup per CU less)
-constexpr int kWgWaves = 4, kWgRows = 2, kWgChunksPerWave = 192;
-constexpr long kWgMinWaves = 4 * 8192;            // the staged kernel only for launches of several rounds of waves (batched periods): ONE
-                                                  // member's period alone is 12 % slower that way (two barriers and a serial prologue per
-                                                  // workgroup with nothing to overlap them), so single launches keep the global path
-constexpr int wg_chunks(int nw) { return nw * kWgChunksPerWave; }   // 16-byte chunks per source window (12 KB for 4 waves)
+// Shape of the staged kernel (kWgWaves, kWgRows, kWgChunksPerWave, and kWgMinWaves: from which launch size on it runs): hf_launch_plan.h.
 
 typedef unsigned short ushort2w __attribute__((ext_vector_type(2)));
 // min / max of both unsigned 16-bit halves (v_pk_min_u16 / v_pk_max_u16)
@@ -1337,10 +1315,7 @@ static_assert(sizeof(WarpArgs) == 168, "hf_kernels.h kMaxWarpBatch is sized for 
 // Block order per member: "super rows" = [plane-building blocks,] two luma block rows, then the chroma block row of the same
 // picture region (a chroma block of NW stacked tiles spans twice the picture rows of a luma block), so that a region's luma and
 // chroma rows pass through L2 at about the same time.
-__host__ __device__ __forceinline__ int wg_super_rows(int yb, int ub) { return ub > (yb + 1) / 2 ? ub : (yb + 1) / 2; }
-__host__ __device__ __forceinline__ int wg_blocks_per_member(int wpr, int yb, int ub, int plane_blocks) {
-    return (wpr * 3 + plane_blocks) * wg_super_rows(yb, ub);
-}
+// (wg_super_rows / wg_blocks_per_member: hf_launch_plan.h -- the launch plan sizes the grid with the same two functions.)
 
 // (88 VGPRs = 5 waves per SIMD; amdgpu_waves_per_eu(6) = 80 VGPRs + 16 spilled: 77.4-77.8 vs 78.0-78.2 k frames/s -- not kept)
 template <typename E, int MODE, int NW, int ROWS>
@@ -1432,30 +1407,17 @@ __global__ void rcp_probe_kernel(const float* in, float* out, int n) {
 // launchers
 // ------------------------------------------------------------------------------------------
 void launch_blur_flow(const Geom& g, const BlurBatch& b, int radius, int zero_count, hipStream_t stream) {
-    // the window-sum form of blur_flow_kernel<32, 4> applies (same test as in the kernel): then 32 x 32 tiles are the faster ones at every batch size
-    const FlowLevel& L = b.s[0].last;
-    const bool window_sums = L.tx && L.ty && L.log2w == 1 && !(g.lw & 1) && !(g.lh & 1) && g.lw >= 64 && g.lh >= 64 && L.nwx * 2 == g.lw && L.nwy * 2 == g.lh;
-    if (radius == 4 && (b.n > 4 || window_sums)) {   // the reference's radius: 32 x 32 outputs per workgroup, taps unrolled (with the tap loops a single
-                                                     // pair is faster with four times the workgroups: 4.3 vs 6.0 us)
-        const dim3 grd((g.lw + 31) / 32, (g.lh + 31) / 32, b.n);
-        const int T = 32 + 8;
-        const size_t smem = (size_t)T * (T + 1) * sizeof(uint32_t) + 2 * (size_t)T * 32 * sizeof(int);   // 16.8 KB (odd row pitch, see the kernel)
-        HF_LAUNCH("blur", (blur_flow_kernel<32, 4>), grd, dim3(256), smem, stream, b, g.lw, g.lh, radius, zero_count);
-        return;
+    const BlurPlan P = plan_blur(g, b.n, b.s[0].last, radius);
+    const dim3 grd(P.grid_x, P.grid_y, b.n);
+    if (P.kernel == kBlur32x4WindowSums || P.kernel == kBlur32x4Taps) {
+        HF_LAUNCH("blur", (blur_flow_kernel<32, 4>), grd, dim3(256), P.lds_bytes, stream, b, g.lw, g.lh, radius, zero_count);
+    } else if (P.kernel == kBlur32x0) {
+        HF_LAUNCH("blur", (blur_flow_kernel<32, 0>), grd, dim3(256), P.lds_bytes, stream, b, g.lw, g.lh, radius, zero_count);
+    } else {
+        if (P.lds_bytes > 48 * 1024)     // large radii (up to 64: 101 KB of the CU's 160 KB LDS) need the opt-in; the attribute is per device
+            (void)hipFuncSetAttribute((const void*)blur_flow_kernel<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        HF_LAUNCH("blur", (blur_flow_kernel<16, 0>), grd, dim3(256), P.lds_bytes, stream, b, g.lw, g.lh, radius, zero_count);
     }
-    if (window_sums && radius >= 2 && radius <= 64 && !(radius & 1)) {   // any even radius in the window-sum form (blur_flow_kernel<32, 0>)
-        const dim3 grd((g.lw + 31) / 32, (g.lh + 31) / 32, b.n);
-        const int nw = 16 + radius;
-        const size_t smem = (size_t)nw * nw * sizeof(uint32_t) + 2 * (size_t)nw * 17 * sizeof(int) + 2 * 17 * 17 * sizeof(int);   // 18 KB at radius 32, 39 KB at 64
-        HF_LAUNCH("blur", (blur_flow_kernel<32, 0>), grd, dim3(256), smem, stream, b, g.lw, g.lh, radius, zero_count);
-        return;
-    }
-    const dim3 grd((g.lw + 15) / 16, (g.lh + 15) / 16, b.n);
-    const int T = 16 + 2 * radius;
-    const size_t smem = (size_t)T * (T + 1) * sizeof(uint32_t) + 2 * (size_t)T * 16 * sizeof(int);
-    if (smem > 48 * 1024)     // large radii (up to 64: 101 KB of the CU's 160 KB LDS) need the opt-in; the attribute is per device
-        (void)hipFuncSetAttribute((const void*)blur_flow_kernel<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    HF_LAUNCH("blur", (blur_flow_kernel<16, 0>), grd, dim3(256), smem, stream, b, g.lw, g.lh, radius, zero_count);
 }
 
 void launch_pack_flow(const Geom& g, const int16_t* flow, uint32_t* packed, hipStream_t stream) {
@@ -1463,240 +1425,135 @@ void launch_pack_flow(const Geom& g, const int16_t* flow, uint32_t* packed, hipS
     pack_flow_kernel<<<(n + 255) / 256, 256, 0, stream>>>(flow, packed, n);
 }
 
-// Fast-path launch for VB bytes per thread and row (all members of `b` in one launch).  Returns false when the
-// shape of any member does not qualify.
-// Does the fast kernel with VB bytes per thread and row apply to every member of `b`?  dw: dword-aligned source loads possible.
-template <typename E, int VB>
-static bool warp_fast_shape(const Geom& g, const WarpBatchArgs& b, bool& dw) {
-    constexpr int VEC = VB / sizeof(E);
-    const int cell = 1 << g.rs;
-    const int group = cell < VEC ? cell : VEC;
-    const int mode = b.s[0].mode;
-    bool fast = mode >= 0 && mode <= 2 && (g.in_stride % 2) == 0 && (g.out_stride % VEC) == 0 &&
-                g.W >= 2 * VEC && group >= 2 && VEC % group == 0 && VEC / group <= 4;   // (group >= 2: a chroma run is made of element PAIRS)
-    // dword-aligned source loads (load_run_dw) need dword-aligned frames and rows that end on a dword
-    dw = ((size_t)g.in_stride * sizeof(E)) % 4 == 0 && ((size_t)g.W * sizeof(E)) % 4 == 0 && ((size_t)g.H * g.in_stride * sizeof(E)) % 4 == 0;
-    for (int m = 0; m < b.n && fast; m++) {
-        const WarpArgs& a = b.s[m];
-        // blend shortcuts of the fast kernel need 0 <= t <= 1 and levels that cannot produce NaN;
-        // chroma runs are read with element-pair granularity: needs an even input stride
-        const bool sane = a.white != a.black && a.white != 0.0f && a.white == a.white && a.black == a.black;
-        fast = fast && a.mode == mode && (mode != 2 || sane) && a.flow_xy && a.n_out >= 1 && a.n_out <= kMaxWarpOutputs;
-        for (int i = 0; i < a.n_out && fast; i++)
-            fast = fast && a.s12v[i] >= 0.0f && a.s12v[i] <= 1.0f && (((uintptr_t)a.outv[i]) & (VB - 1)) == 0;
-        dw = dw && (((uintptr_t)a.frame12 | (uintptr_t)a.frame21) & 3) == 0;
-    }
-    return fast;
-}
-template <typename E>
-static constexpr bool warp_small_frame(const Geom& g) {   // frames up to 1080p 8-bit: 8 bytes per thread (twice the waves)
-    return (size_t)g.W * g.H * sizeof(E) <= (size_t)1920 * 1088;
-}
-
-// Can the staged kernel build the phase planes of its members' frame21 (emit_plane_rows)?  The geometry part of the answer.
-static bool plane_emission_geometry(const Geom& g, const PhaseLayout& pl) {   // = the conditions of the fast plane kernel (hf_flow.hip launch_prep_fast)
-    const size_t esz = g.hdr ? 2 : 1;
-    const int lw = g.W >> g.rs;
-    return g.rs >= 3 && g.rs <= 4 && pl.rs == g.rs && (lw << g.rs) == g.W && lw == g.lw && (lw & 3) == 0 && pl.mx <= lw && (pl.mx & 3) == 0 &&
-           (pl.lwp & 3) == 0 && ((size_t)g.in_stride * esz) % 16 == 0 && ((size_t)g.H * g.in_stride * esz) % 16 == 0 && (g.H & 1) == 0;
-}
-
-template <typename E, int VB>
-static bool launch_warp_fast(const Geom& g, const WarpBatchArgs& b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                             const PhaseLayout* pl = nullptr, bool* planes_built = nullptr) {
-    constexpr int VEC = VB / sizeof(E);
-    const int cell = 1 << g.rs;
-    const int group = cell < VEC ? cell : VEC;
-    const int mode = b.s[0].mode;
-    bool dw = false;
-    if (!warp_fast_shape<E, VB>(g, b, dw)) return false;
-    if (t_launch_observer && !ev0 && !ev1) {   // timeline (hf_kernels.h): the dispatch carries the observer's events
-        hipEvent_t o0 = nullptr, o1 = nullptr;
-        if (t_launch_observer->next("warp_period", &o0, &o1)) { ev0 = o0; ev1 = o1; }
-    }
-    const int rows = 2;  // rows per thread (divides the 2^rs rows of a flow cell); measured on MI355X, 2160p HDR blend: 1 row 25.9 us, 2 rows 24.3 us, 4 rows 30.2 us
-                         // (re-measured with the final kernel, fused period HBM-cold: 2 rows 51.1 us, 4 rows 59.3 us -- halving the
-                         // per-element scalar work does not pay for halving the number of waves)
-    const int y_groups = (g.H + rows - 1) / rows, uv_groups = ((g.H >> 1) + rows - 1) / rows;
-    const int wpr = (g.W + kWarpTX * VEC - 1) / (kWarpTX * VEC);
-    const int n_tiles = wpr * ((y_groups + kWarpTY - 1) / kWarpTY + (uv_groups + kWarpTY - 1) / kWarpTY);
-    int max_out = 1;
-    for (int m = 0; m < b.n; m++) max_out = b.s[m].n_out > max_out ? b.s[m].n_out : max_out;
-    // outputs per thread: everything for large frames; one for frames up to 1080p (measured, fused 5-output period, us:
-    // 1080p SDR 23.6 / 21.9 / 20.3 / 18.9 and 1080p HDR 19.0 / 19.1 with 6 / 3 / 2 / 1 outputs per thread; 2160p HDR
-    // 45.9 / 46.6 hot, 50.8 / 52.1 HBM-cold with 6 / 1)
-    // ... unless the launch has rounds of waves to spare (batched periods): then every thread produces all outputs there too
-    // (1080p SDR 24 -> 60, 2 batches of 16: 107.9 -> 114.2 k frames/s)
-    const bool small_frame = (size_t)g.W * g.H * sizeof(E) <= (size_t)1920 * 1088 * 2;
-    const int out_chunk = small_frame && (long)n_tiles * b.n < 4 * 8192 ? 1 : kMaxWarpOutputs;
-    const int n_chunks = (max_out + out_chunk - 1) / out_chunk;
-    // large workgroups only where the launch keeps every CU supplied with them (>= 4 rounds of 8,192 resident waves)
-    // one LDS window per workgroup of kWgWaves stacked wave tiles (warp_wg_kernel): one flow cell per 16-byte thread, all outputs of the
-    // period per thread, dword-aligned frames, launches of several rounds of waves (inside the pipeline the staged launch is 10 % shorter
-    // than the global path -- 1,385 vs 1,545-1,595 us per 16 members, round 3)
-    constexpr int WR = kWgRows, NW = kWgWaves * 2 / WR;                        // rows per thread, waves per workgroup (tile height kWgWaves x 8 rows)
-    const int y_tiles_ = (((g.H + WR - 1) / WR) + kWarpTY - 1) / kWarpTY, uv_tiles_ = ((((g.H >> 1) + WR - 1) / WR) + kWarpTY - 1) / kWarpTY;
-    const int plane_blocks = ((g.lw >> 2) * (2 * NW * kWarpTY * WR) + 64 * NW - 1) / (64 * NW);   // (groups of 4 columns) x (luma rows of a super row) tasks
-    // (its workgroups decode their unit index with scalar multiply-high divisions, exact while units x blocks per member < 2^32: frames
-    //  far beyond 8K take the generic launch below)
-    const uint32_t nb_max = (uint32_t)wg_blocks_per_member(wpr, (y_tiles_ + NW - 1) / NW, (uv_tiles_ + NW - 1) / NW, plane_blocks);
-    if constexpr (VB == 16) if (group == VEC && dw && out_chunk > 1 && max_out >= 2 && (long)n_tiles * b.n >= kWgMinWaves &&
-                                fastdiv_exact((uint64_t)nb_max * b.n + 8, nb_max)) {
-        // deferred phase planes: members that ask for one (plane21) get it from this launch if geometry and alignment allow
-        WarpBatchArgs bb = b;
-        PlaneOut po{};
-        po.counters = b.counters;
-        bool emit = pl && plane_emission_geometry(g, *pl);
-        for (int m = 0; m < bb.n; m++)
-            if (!emit || (((uintptr_t)bb.s[m].frame21) & 15) != 0) bb.s[m].plane21 = nullptr;
-        emit = false;
-        for (int m = 0; m < bb.n; m++) emit = emit || bb.s[m].plane21 != nullptr;
-        if (planes_built) for (int m = 0; m < bb.n; m++) planes_built[m] = bb.s[m].plane21 != nullptr;
-        if (emit) {
-            po.pl = *pl;
-            po.blocks = plane_blocks;
-        }
-        const int nb = wg_blocks_per_member(wpr, (y_tiles_ + NW - 1) / NW, (uv_tiles_ + NW - 1) / NW, po.blocks);
-        const uint64_t max_unit = (uint64_t)nb * b.n + 8;   // (units of a launch incl. the padding of its grid to a multiple of 8)
-        po.per_member = make_fastdiv((uint32_t)nb, max_unit); po.per_sr = make_fastdiv((uint32_t)(wpr * 3 + po.blocks), (uint64_t)nb);
-        po.wpr = make_fastdiv((uint32_t)wpr, (uint64_t)wpr * 3 + po.blocks);
-        const dim3 wg(((nb * b.n + 7) / 8) * 8), wb(64 * NW);
-        const size_t lds_bytes = (size_t)2 * wg_chunks(NW * WR / 2) * 16;
-#define HF_WARP_WG_LAUNCH(M)                                                                                                                  \
-        do {                                                                                                                                      \
-            auto kern = warp_wg_kernel<E, M, NW, WR>;                                                                                                 \
-            if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);  \
-            hipExtLaunchKernelGGL(kern, wg, wb, lds_bytes, stream, ev0, ev1, 0, g, bb, po);                                             \
-        } while (0)
-        if (mode == 0) HF_WARP_WG_LAUNCH(0);
-        else if (mode == 1) HF_WARP_WG_LAUNCH(1);
-        else HF_WARP_WG_LAUNCH(2);
-#undef HF_WARP_WG_LAUNCH
-        return true;
-    }
-    // large workgroups only where the launch keeps every CU supplied with them (>= 4 rounds of 8,192 resident waves)
-    const int wpb = out_chunk > 1 && (long)n_tiles * n_chunks * b.n >= 4 * 8192 ? warp_max_waves(sizeof(E), group, VB) : kWarpWavesSmall;
-    const int n_blocks = (n_tiles + wpb - 1) / wpb;
-    const dim3 fg(((n_blocks * n_chunks * b.n + 7) / 8) * 8), fb(64 * wpb);
-#define HF_WARP_FAST(G, D)                                                                   \
-    do {                                                                                     \
-        /* ev0/ev1 (may be null): timestamps of the dispatch itself, like rocprof's kernel trace */ \
-        if (mode == 0) hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 0, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, y_groups, out_chunk, n_chunks);      \
-        else if (mode == 1) hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 1, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, y_groups, out_chunk, n_chunks); \
-        else hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 2, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, y_groups, out_chunk, n_chunks);                  \
-    } while (0)
-#define HF_WARP_GROUP(D)                                  \
-    do {                                                  \
-        if (group == VEC) HF_WARP_FAST(VEC, D);           \
-        else if (group == VEC / 2) HF_WARP_FAST(VEC / 2, D); \
-        else HF_WARP_FAST(VEC / 4, D);                    \
-    } while (0)
-    if (dw) HF_WARP_GROUP(true);
-    else HF_WARP_GROUP(false);
-#undef HF_WARP_GROUP
-#undef HF_WARP_FAST
-    return true;
-}
-
-// frames up to 1080p 8-bit: 8 bytes per thread (twice the waves); larger frames: 16 bytes per thread
-template <typename E>
-static bool launch_warp_fast_any(const Geom& g, const WarpBatchArgs& b, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                                 const PhaseLayout* pl = nullptr, bool* planes_built = nullptr) {
-    const bool small = warp_small_frame<E>(g);   // (1080p SDR, 5-output period: 18.9 us with 8-byte threads, 26.8 us with 16-byte ones)
-    if (small && launch_warp_fast<E, 8>(g, b, stream, ev0, ev1)) return true;   // (also in a batch of 16: 114.3 k frames/s against 100.2 k with 16-byte threads)
-    return launch_warp_fast<E, 16>(g, b, stream, ev0, ev1, pl, planes_built);
-}
-
-template <typename E>
-static void launch_warp_t(const Geom& g, const WarpArgs& a, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-    constexpr int VEC = 16 / sizeof(E);  // generic kernel: 16-byte stores
-    WarpBatchArgs b;
-    b.n = 1; b.counters = nullptr; b.s[0] = a;
-    if (launch_warp_fast_any<E>(g, b, stream, ev0, ev1)) return;
-    const bool aligned = (g.out_stride % VEC) == 0 && (((uintptr_t)a.out) & 15) == 0;
-    const dim3 grd((g.W + 64 * VEC - 1) / (64 * VEC), (g.H + (g.H >> 1) + 3) / 4);
-    if (aligned) hipExtLaunchKernelGGL((warp_kernel<E, VEC, true>), grd, dim3(256), 0, stream, ev0, ev1, 0, g, a);
-    else hipExtLaunchKernelGGL((warp_kernel<E, VEC, false>), grd, dim3(256), 0, stream, ev0, ev1, 0, g, a);
-}
-
-void launch_warp(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
-                 void* out, float t, int mode, float black, float white, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-    WarpArgs a;
-    a.frame12 = frame12; a.frame21 = frame21; a.flow = flow; a.flow_xy = flow_xy; a.out = out;
-    a.s12 = t; a.s21 = 1.0f - t; a.mode = mode; a.black = black; a.white = white;
-    a.n_out = 1; a.s12v[0] = a.s12; a.s21v[0] = a.s21; a.outv[0] = out; a.plane21 = nullptr;
-    if (g.hdr) launch_warp_t<uint16_t>(g, a, stream, ev0, ev1);
-    else launch_warp_t<uint8_t>(g, a, stream, ev0, ev1);
-}
-
-// Launch arguments of members [first, first + b.n) of a set of periods; false: a member's n_out is out of range.
-static bool fill_warp_batch(const WarpPeriod* periods, int n, int first, int mode, WarpBatchArgs& b) {
-    b.n = n - first < kMaxWarpBatch ? n - first : kMaxWarpBatch;
+// Launch arguments of the members of one planned launch.
+static void fill_warp_batch(const WarpPeriod* periods, const WarpLaunch& L, int mode, WarpBatchArgs& b) {
+    b.n = L.count;
     b.counters = periods[0].counters;
     for (int m = 0; m < b.n; m++) {
-        const WarpPeriod& p = periods[first + m];
-        if (p.n_out < 1 || p.n_out > kMaxWarpOutputs) return false;
+        const WarpPeriod& p = periods[L.first + m];
         WarpArgs& a = b.s[m];
         a.frame12 = p.frame12; a.frame21 = p.frame21; a.flow = p.flow; a.flow_xy = p.flow_xy; a.out = p.outs[0];
         a.mode = mode; a.black = p.black; a.white = p.white;
         a.n_out = p.n_out;
         for (int i = 0; i < p.n_out; i++) { a.s12v[i] = p.ts[i]; a.s21v[i] = 1.0f - p.ts[i]; a.outv[i] = p.outs[i]; }
         a.s12 = a.s12v[0]; a.s21 = a.s21v[0];
-        a.plane21 = p.plane21;
+        a.plane21 = (L.planes >> m) & 1u ? p.plane21 : nullptr;   // (only the members whose plane this launch builds keep the pointer)
     }
-    return true;
 }
+
+// A planned launch (hf_launch_plan.h) as template arguments.  ev0/ev1 (may be null): timestamps of the dispatch itself, like rocprof's kernel trace.
+template <typename E, int VB>
+static void dispatch_warp_fast(const Geom& g, const WarpLaunch& L, const WarpBatchArgs& b, int mode, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    constexpr int VEC = VB / sizeof(E);
+    static_assert(kWarpFastRows == 2, "the fast kernels are instantiated for two rows per thread");
+    const dim3 fg(L.grid), fb(L.block);
+#define HF_WARP_FAST(G, D)                                                                   \
+    do {                                                                                     \
+        if (mode == 0) hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 0, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, L.y_groups, L.out_chunk, L.n_chunks);      \
+        else if (mode == 1) hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 1, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, L.y_groups, L.out_chunk, L.n_chunks); \
+        else hipExtLaunchKernelGGL((warp_fast_kernel<E, G, 2, 2, VB, D>), fg, fb, 0, stream, ev0, ev1, 0, g, b, L.y_groups, L.out_chunk, L.n_chunks);                  \
+    } while (0)
+#define HF_WARP_GROUP(D)                                  \
+    do {                                                  \
+        if (L.group == VEC) HF_WARP_FAST(VEC, D);           \
+        else if (L.group == VEC / 2) HF_WARP_FAST(VEC / 2, D); \
+        else HF_WARP_FAST(VEC / 4, D);                    \
+    } while (0)
+    if (L.dw) HF_WARP_GROUP(true);
+    else HF_WARP_GROUP(false);
+#undef HF_WARP_GROUP
+#undef HF_WARP_FAST
+}
+
 template <typename E>
-static bool warp_fast_any_shape(const Geom& g, const WarpBatchArgs& b) {
-    bool dw = false;
-    return (warp_small_frame<E>(g) && warp_fast_shape<E, 8>(g, b, dw)) || warp_fast_shape<E, 16>(g, b, dw);
+static void dispatch_warp_staged(const Geom& g, const WarpLaunch& L, const WarpBatchArgs& b, int mode, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                                 const PhaseLayout* pl) {
+    constexpr int WR = kWgRows, NW = kWgWaves * 2 / WR;                        // rows per thread, waves per workgroup (tile height kWgWaves x 8 rows)
+    PlaneOut po{};
+    po.counters = b.counters;
+    if (L.planes) po.pl = *pl;
+    po.blocks = L.plane_blocks;
+    po.per_member = make_fastdiv((uint32_t)L.blocks_per_member, L.max_unit);
+    po.per_sr = make_fastdiv((uint32_t)(L.wpr * 3 + L.plane_blocks), (uint64_t)L.blocks_per_member);
+    po.wpr = make_fastdiv((uint32_t)L.wpr, (uint64_t)L.wpr * 3 + L.plane_blocks);
+    const dim3 wg(L.grid), wb(L.block);
+    const size_t lds_bytes = L.lds_bytes;
+#define HF_WARP_WG_LAUNCH(M)                                                                                                                  \
+        do {                                                                                                                                      \
+            auto kern = warp_wg_kernel<E, M, NW, WR>;                                                                                                 \
+            if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);  \
+            hipExtLaunchKernelGGL(kern, wg, wb, lds_bytes, stream, ev0, ev1, 0, g, b, po);                                              \
+        } while (0)
+    if (mode == 0) HF_WARP_WG_LAUNCH(0);
+    else if (mode == 1) HF_WARP_WG_LAUNCH(1);
+    else HF_WARP_WG_LAUNCH(2);
+#undef HF_WARP_WG_LAUNCH
+}
+
+template <typename E>
+static void dispatch_warp(const Geom& g, const WarpLaunch& L, const WarpBatchArgs& b, int mode, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                          const PhaseLayout* pl) {
+    if (t_launch_observer && !ev0 && !ev1) {   // timeline (hf_kernels.h): the dispatch carries the observer's events
+        hipEvent_t o0 = nullptr, o1 = nullptr;
+        if (t_launch_observer->next("warp_period", &o0, &o1)) { ev0 = o0; ev1 = o1; }
+    }
+    // (kernels are emitted into the code object in the order they are first named: 8-byte threads, staged, 16-byte threads)
+    if (L.family == kWarpFast && L.vb == 8) dispatch_warp_fast<E, 8>(g, L, b, mode, stream, ev0, ev1);
+    else if (L.family == kWarpStaged) dispatch_warp_staged<E>(g, L, b, mode, stream, ev0, ev1, pl);
+    else dispatch_warp_fast<E, 16>(g, L, b, mode, stream, ev0, ev1);
+}
+
+template <typename E>
+static void launch_warp_generic(const Geom& g, const WarpArgs& a, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    constexpr int VEC = 16 / sizeof(E);  // generic kernel: 16-byte stores
+    const PlanePassPlan P = plan_warp_generic(g, a.out);
+    const dim3 grd(P.grid_x, P.grid_y);
+    if (P.aligned) hipExtLaunchKernelGGL((warp_kernel<E, VEC, true>), grd, dim3(P.block), 0, stream, ev0, ev1, 0, g, a);
+    else hipExtLaunchKernelGGL((warp_kernel<E, VEC, false>), grd, dim3(P.block), 0, stream, ev0, ev1, 0, g, a);
+}
+
+void launch_warp(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
+                 void* out, float t, int mode, float black, float white, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    WarpPeriod p{};   // (no counters: a single context's one-output launch is not counted -- and is never staged, that needs two outputs)
+    p.frame12 = frame12; p.frame21 = frame21; p.flow = flow; p.flow_xy = flow_xy;
+    p.n_out = 1; p.outs[0] = out; p.ts[0] = t; p.black = black; p.white = white;
+    const WarpPlan P = plan_warp_periods(g, 1, &p, mode, nullptr);
+    WarpLaunch one{};   // (the arguments of the generic kernel are member 0's of a one-member launch)
+    one.count = 1;
+    WarpBatchArgs b;
+    fill_warp_batch(&p, P.n_launches ? P.launch[0] : one, mode, b);
+    if (!P.n_launches) {
+        if (g.hdr) launch_warp_generic<uint16_t>(g, b.s[0], stream, ev0, ev1);
+        else launch_warp_generic<uint8_t>(g, b.s[0], stream, ev0, ev1);
+    } else if (g.hdr) dispatch_warp<uint16_t>(g, P.launch[0], b, mode, stream, ev0, ev1, nullptr);
+    else dispatch_warp<uint8_t>(g, P.launch[0], b, mode, stream, ev0, ev1, nullptr);
 }
 
 bool launch_warp_periods(const Geom& g, int n, const WarpPeriod* periods, int mode, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                          const PhaseLayout* pl, bool* planes_built) {
     if (planes_built) for (int m = 0; m < n; m++) planes_built[m] = false;
-    if (n < 1 || n > kMaxFlowBatch) return false;
     // at most kMaxWarpBatch members per launch (kernel-argument space): a batch of 32 is two launches.  ALL of them are
-    // checked before the first one goes out, so a set of periods is either rendered by these launches or not touched at all
-    for (int first = 0; first < n; first += kMaxWarpBatch) {
+    // planned before the first one goes out, so a set of periods is either rendered by these launches or not touched at all
+    const WarpPlan P = plan_warp_periods(g, n, periods, mode, pl);
+    for (int i = 0; i < P.n_launches; i++) {
+        const WarpLaunch& L = P.launch[i];
         WarpBatchArgs b;
-        if (!fill_warp_batch(periods, n, first, mode, b)) return false;
-        if (!(g.hdr ? warp_fast_any_shape<uint16_t>(g, b) : warp_fast_any_shape<uint8_t>(g, b))) return false;
+        fill_warp_batch(periods, L, mode, b);
+        if (planes_built) for (int m = 0; m < L.count; m++) planes_built[L.first + m] = (L.planes >> m) & 1u;
+        hipEvent_t e0 = i == 0 ? ev0 : nullptr, e1 = i == P.n_launches - 1 ? ev1 : nullptr;
+        if (g.hdr) dispatch_warp<uint16_t>(g, L, b, mode, stream, e0, e1, pl);
+        else dispatch_warp<uint8_t>(g, L, b, mode, stream, e0, e1, pl);
     }
-    for (int first = 0; first < n; first += kMaxWarpBatch) {
-        WarpBatchArgs b;
-        fill_warp_batch(periods, n, first, mode, b);
-        hipEvent_t e0 = first == 0 ? ev0 : nullptr, e1 = first + kMaxWarpBatch >= n ? ev1 : nullptr;
-        bool* pb = planes_built ? planes_built + first : nullptr;
-        const bool ok = g.hdr ? launch_warp_fast_any<uint16_t>(g, b, stream, e0, e1, pl, pb) : launch_warp_fast_any<uint8_t>(g, b, stream, e0, e1, pl, pb);
-        if (!ok) return false;   // (cannot happen after the check above)
-    }
-    return true;
-}
-
-bool warp_period_can_build_planes(const Geom& g, const PhaseLayout& pl, int n_members) {
-    const size_t esz = g.hdr ? 2 : 1;
-    const int VEC = (int)(16 / esz), cell = 1 << g.rs;
-    // one flow cell per 16-byte thread, no 8-byte threads.  (Frames that take warp_fast_kernel -- 1080p and smaller -- keep their eager planes:
-    // plane-building workgroups in THAT launch were built and measured in round 5, bit-exact and 2 % slower than the stand-alone plane kernel
-    // there: 131.3-131.7 k against 134.0-134.5 k frames/s at 1080p SDR -- the frame is small enough to be re-read from L2, and the deferred order
-    // adds the grid-sample launch; tools/attic/r05/deferred_planes_fast_kernel.diff)
-    if (cell < VEC || (size_t)g.W * g.H * esz <= (size_t)1920 * 1088) return false;
-    const int y_groups = (g.H + 1) / 2, uv_groups = ((g.H >> 1) + 1) / 2;
-    const int wpr = (g.W + kWarpTX * VEC - 1) / (kWarpTX * VEC);
-    const long n_tiles = (long)wpr * ((y_groups + kWarpTY - 1) / kWarpTY + (uv_groups + kWarpTY - 1) / kWarpTY);
-    const int per_launch = n_members < kMaxWarpBatch ? n_members : kMaxWarpBatch;
-    return n_tiles * per_launch >= kWgMinWaves && g.H == (g.lh << g.rs) && plane_emission_geometry(g, pl);
+    return P.n_launches > 0;
 }
 
 template <typename E>
 static void launch_copy_t(const Geom& g, const void* src, void* out, float black, float white, hipStream_t stream) {
     constexpr int VEC = 16 / sizeof(E);
-    const bool aligned = (g.in_stride % VEC) == 0 && (g.out_stride % VEC) == 0 &&
-                         (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
-    const dim3 grd((g.W + 64 * VEC - 1) / (64 * VEC), (g.H + (g.H >> 1) + 3) / 4);
-    if (aligned) copy_kernel<E, VEC, true><<<grd, 256, 0, stream>>>(g, (const E*)src, (E*)out, black, white);
-    else copy_kernel<E, VEC, false><<<grd, 256, 0, stream>>>(g, (const E*)src, (E*)out, black, white);
+    const PlanePassPlan P = plan_copy(g, src, out);
+    const dim3 grd(P.grid_x, P.grid_y);
+    if (P.aligned) copy_kernel<E, VEC, true><<<grd, P.block, 0, stream>>>(g, (const E*)src, (E*)out, black, white);
+    else copy_kernel<E, VEC, false><<<grd, P.block, 0, stream>>>(g, (const E*)src, (E*)out, black, white);
 }
 
 void launch_copy(const Geom& g, const void* src, void* out, float black, float white, hipStream_t stream) {

@@ -1,9 +1,9 @@
-"""CPU model of which kernel instantiation the batched chain and the blur launch (csrc/hf_flow.hip launch_flow_level_small,
-launch_flow_big_partial; csrc/hf_kernels.hip launch_blur_flow; csrc/hf_calc.hip enqueue_flow_chain, choose_tab_mode).
+"""CPU model of which kernel instantiation the batched chain and the blur launch (csrc/hf_launch_plan.h plan_flow_level_small,
+plan_flow_big_waves, plan_sad_tables, plan_blur; csrc/hf_calc.hip enqueue_flow_chain, choose_tab_mode).
 
 The launchers choose by more than the frame geometry: the batch size, the resolution scalar, the search radius and the table mode each
 select another instantiation, and inside a kernel a tile's position selects the body.  This module restates those selectors in Python,
-tests/test_chain_variant_model.py pins its constants to the sources, and CASES -- the matrix tests/test_chain_variants_gpu.py runs against
+it is compared with the launchers' plan functions by tests/test_chain_variant_model.py, and CASES -- the matrix tests/test_chain_variants_gpu.py runs against
 the oracle -- must reach every variant and every (variant, tile class) pair the model knows.
 
 Variant labels
@@ -27,7 +27,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import oracle  # noqa: E402  (test infrastructure)
 
-# thresholds of the launchers (pinned to the sources by tests/test_chain_variant_model.py)
+# thresholds of the launchers (compared with the launchers' plan functions by tests/test_chain_variant_model.py)
 ROW_PER_LANE_MAX_BATCH = 4        # hf_flow.hip kRowPerLaneMaxBatch
 LEVEL32_ONE_WAVE_MIN_BATCH = 4    # HF_LEVEL32_ONE_WAVE_MIN_BATCH
 BIG_ONE_WAVE_MIN_BATCH = 4        # HF_BIG_ONE_WAVE_MIN_BATCH

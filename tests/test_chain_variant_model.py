@@ -1,4 +1,5 @@
-"""CPU: the model of the chain's and the blur's variant selection (tests/chain_variant_model.py) is pinned to the sources, and the matrix
+"""CPU: the model of the chain's and the blur's variant selection (tests/chain_variant_model.py) is compared with the launchers' own plan
+functions (csrc/hf_launch_plan.h, called through tests/launch_plan_probe.cpp), and the matrix
 that tests/test_chain_variants_gpu.py runs against the oracle reaches every variant and every (variant, tile class) pair the model knows.
 A changed threshold in the launchers fails here until the matrix has been reconsidered.  Also: the window-sum blur's gather indices stay
 inside the offset tables (the condition the bounds build checks on the device at site 201)."""
@@ -10,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chain_variant_model as M  # noqa: E402
+import launch_plan_probe  # noqa: E402
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hopperrender_amd", "csrc")
 
@@ -25,24 +27,115 @@ def _int(text, pattern):
     return int(m[0])
 
 
-def test_thresholds_equal_the_sources():
-    flow, kern, kern_h, calc = _src("hf_flow.hip"), _src("hf_kernels.hip"), _src("hf_kernels.h"), _src("hf_calc.hip")
-    assert _int(flow, r"constexpr int kRowPerLaneMaxBatch = (\d+);") == M.ROW_PER_LANE_MAX_BATCH
-    assert _int(flow, r"#define HF_LEVEL32_ONE_WAVE_MIN_BATCH (\d+)") == M.LEVEL32_ONE_WAVE_MIN_BATCH
-    assert _int(flow, r"#define HF_BIG_ONE_WAVE_MIN_BATCH (\d+)") == M.BIG_ONE_WAVE_MIN_BATCH
-    assert _int(flow, r"kBigOneWaveMinRs = (\d+)[,;]") == M.BIG_ONE_WAVE_MIN_RS
-    assert _int(kern_h, r"constexpr int kMaxFlowBatch = (\d+);") == M.MAX_FLOW_BATCH
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return launch_plan_probe.load(tmp_path_factory.mktemp("launch_plan_probe"))
+
+
+def test_thresholds_equal_the_sources(probe):
+    """The thresholds of hf_launch_plan.h as the compiled header has them; those of the API layer and of the kernel by their lines."""
+    k, kern, calc = probe.constants, _src("hf_kernels.hip"), _src("hf_calc.hip")
+    assert k["kRowPerLaneMaxBatch"] == M.ROW_PER_LANE_MAX_BATCH
+    assert k["kLevel32OneWaveMinBatch"] == M.LEVEL32_ONE_WAVE_MIN_BATCH
+    assert (k["kBigOneWaveMinBatch"], k["kBigOneWaveMinRs"], k["kBigWavesPerBlock"]) == (M.BIG_ONE_WAVE_MIN_BATCH, M.BIG_ONE_WAVE_MIN_RS, 4)
+    assert k["kMaxFlowBatch"] == M.MAX_FLOW_BATCH and k["kBlurWindowSumMinDim"] == M.WINDOW_SUM_MIN_DIM
     assert _int(calc, r"if \(n < (\d+)\) return false;") == M.TABLES_MIN_BATCH
     assert _int(calc, r"const bool use_neighbors = k >= (\d+);") == M.NEIGHBOUR_FIRST_LEVEL
-    # the window-sum condition: once in the kernel, once in the launcher, the same bound
+    # the window-sum condition the kernel re-tests on the device: the same bound
     dims = re.findall(r"lw >= (\d+) && (?:g\.)?lh >= (\d+)", kern)
-    assert len(dims) == 2 and all(d == (str(M.WINDOW_SUM_MIN_DIM),) * 2 for d in dims), dims
-    # the comparisons the model restates
-    assert "b.n <= kRowPerLaneMaxBatch && ws <= 4" in flow and "b.n >= kLevel32OneWaveMinBatch" in flow
-    assert "b.n >= kBigOneWaveMinBatch && g.rs >= kBigOneWaveMinRs ? 1 : kBigWavesPerBlock" in flow
-    assert "b.s[0].sadtab && b.s[0].R == 16 && (b.s[0].sad_read || b.s[0].sad_write)" in flow
-    assert "radius == 4 && (b.n > 4 || window_sums)" in kern and "window_sums && radius >= 2 && radius <= 64 && !(radius & 1)" in kern
-    assert "m->levels[k].window >= 4;" in calc and "k > 0 && m->levels[k - 1].window <= 32;" in calc
+    assert dims == [(str(M.WINDOW_SUM_MIN_DIM),) * 2], dims
+
+
+# ------------------------------------------------------------------------------------------------
+# the model against the launchers' own plan functions (hf_launch_plan.h through tests/launch_plan_probe.cpp)
+# ------------------------------------------------------------------------------------------------
+def model_small_level(n, ws, R, tables_present, sad_read, sad_write):
+    """The fields of a small level's launch as M.launches decides them (one_wave32, rows1, tile_w, waves, tabk, block)."""
+    rows1 = n <= M.ROW_PER_LANE_MAX_BATCH and ws <= 4
+    one_wave = ws == 32 and n >= M.LEVEL32_ONE_WAVE_MIN_BATCH
+    waves = 1 if ws == 32 else 4 if ws >= 8 else (4 if rows1 or ws == 2 else 2)
+    return (int(one_wave), int(rows1), 16 if rows1 and ws == 2 else 32, waves, int(tables_present and R == 16 and (sad_read or sad_write)),
+            256 if ws == 32 and not one_wave else 64)
+
+
+def test_chain_plans_equal_the_model_on_the_grid(probe):
+    """Every n in 1 .. 32, every window 2 .. 256, R in {2, 5, 11, 16}, rs 0 .. 4, tables on / off: the three chain plan functions against the
+    selectors the model's launches() restates; moving a threshold in the header names the inputs that changed kernel here."""
+    windows = [256, 128, 64, 32, 16, 8, 4, 2]
+    for n in range(1, 33):
+        for rs in range(5):
+            assert probe.plan_flow_big_waves(n, rs) == (1 if n >= M.BIG_ONE_WAVE_MIN_BATCH and rs >= M.BIG_ONE_WAVE_MIN_RS else 4), (n, rs)
+        for ws in windows[3:]:
+            for R in (2, 5, 11, 16):
+                for present in (False, True):
+                    for rd, wr in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                        assert tuple(probe.plan_flow_level_small(n, ws, R, present, rd, wr)) == model_small_level(n, ws, R, present, rd, wr), (n, ws, R, present, rd, wr)
+    for first in range(len(windows)):
+        for last in range(first + 1, len(windows) + 1):
+            ws_list = windows[first:last]
+            for k, ws in enumerate(ws_list):
+                for on in (False, True):
+                    want = (on and ws <= 32 and k > 0 and ws_list[k - 1] <= 32, on and 4 <= ws <= 32)
+                    assert probe.plan_sad_tables(ws_list, k, on) == want, (ws_list, k, on)
+
+
+@pytest.mark.parametrize("case", M.CASES, ids=lambda c: c.name)
+def test_chain_plans_equal_the_model_on_the_matrix(probe, case):
+    """Every launch of every case of the matrix, in each table mode the case can run in: the plan's variant is the model's."""
+    g = M.geometry(case)
+    ws_list = M.windows(case, g)
+    for on in ((False, True) if M.tables_on(case) is None else (M.tables_on(case),)):
+        lns = M.launches(case, tab=on)
+        steps = [(k, ws) for k, ws in enumerate(ws_list) for _axis in ((0, 1) if ws > 32 else (0,))]
+        assert len(steps) == len(lns)
+        for (k, ws), ln in zip(steps, lns):
+            kind = ln.variant.rsplit(".", 1)[1]
+            if ws > 32:
+                wpb = probe.plan_flow_big_waves(case.n, g.rs)
+                assert ln.variant == f"big.wave{wpb}.{'r16' if case.R == 16 else 'anyR'}"
+                assert ln.units == -(-g.lw // 64) * -(-g.lh // (4 * wpb)) * case.n
+                continue
+            rd, wr = probe.plan_sad_tables(ws_list, k, on)
+            P = probe.plan_flow_level_small(case.n, ws, case.R, on, rd, wr)
+            name = ("level32.wave" if P.one_wave32 else "level32.four_wave") if ws == 32 else f"level{ws}" if ws >= 8 else f"level{ws}.{'row' if P.rows1 else 'block'}"
+            assert ln.variant == f"{name}.{'tab' if P.tabk else 'plain' if case.R == 16 else 'anyR'}", (case.name, ws, ln.variant, P)
+            assert ln.units == -(-g.lw // P.tile_w) * -(-g.lh // 32) * P.waves * case.n
+            assert (kind == "tab") == bool(P.tabk) and bool(ln.table_windows) == bool(P.tabk)
+    blur = probe.plan_blur(tuple(g_tuple(g)), case.n, case.blur_radius, ws_list[-1] if ws_list else 0)
+    assert launch_plan_probe.BLUR_KERNELS[blur.kernel] == M.blur_variant(case), case.name
+
+
+def g_tuple(g):
+    return (g.hdr, g.H, g.W, g.in_stride, g.out_stride, g.rs, g.lw, g.lh)
+
+
+def model_blur(lw, lh, n, r, last_window):
+    """M.blur_variant's decision and the launch's tile and dynamic LDS bytes (hf_kernels.hip blur_flow_kernel's layouts)."""
+    window_sums = last_window == 2 and not (lw & 1) and not (lh & 1) and lw >= M.WINDOW_SUM_MIN_DIM and lh >= M.WINDOW_SUM_MIN_DIM
+    if r == 4 and (n > 4 or window_sums):
+        return ("blur.32x4.window_sums" if window_sums else "blur.32x4.taps"), 32, 40 * 41 * 4 + 2 * 40 * 32 * 4
+    if window_sums and 2 <= r <= 64 and not (r & 1):
+        return "blur.32x0", 32, (16 + r) ** 2 * 4 + 2 * (16 + r) * 17 * 4 + 2 * 17 * 17 * 4
+    return "blur.16x0", 16, (16 + 2 * r) * (17 + 2 * r) * 4 + 2 * (16 + 2 * r) * 16 * 4
+
+
+def test_blur_plan_equals_the_model_on_the_grid(probe):
+    """Every even and a few odd radii 2 .. 64 on grids 62 .. 162, even and odd, batches on both sides of n > 4, last level 2 or not."""
+    seen = set()
+    for lw in list(range(62, 68)) + [96, 127, 128, 161, 162]:
+        for lh in list(range(62, 68)) + [97, 160, 162]:
+            g = (0, lh * 4, lw * 4, lw * 4, lw * 4, 2, lw, lh)
+            for r in list(range(2, 65, 2)) + [3, 5, 7, 33, 63]:
+                for n in (1, 4, 5, 32):
+                    for last in (2, 4, 32, 0):
+                        P = probe.plan_blur(g, n, r, last)
+                        want = model_blur(lw, lh, n, r, last)
+                        assert (launch_plan_probe.BLUR_KERNELS[P.kernel], P.tile, P.lds_bytes) == want, (lw, lh, r, n, last, P)
+                        assert (P.grid_x, P.grid_y) == (-(-lw // P.tile), -(-lh // P.tile))
+                        seen.add(want[0])
+    # a last level of 2 whose tables do not cover the grid (never built by the API layer) has no window sums
+    assert launch_plan_probe.BLUR_KERNELS[probe.plan_blur((0, 256, 256, 256, 256, 2, 64, 64), 1, 4, 2, nwx=31).kernel] == "blur.16x0"
+    assert seen == set(launch_plan_probe.BLUR_KERNELS)
 
 
 def test_batch_argument_limit():

@@ -1,5 +1,5 @@
 """GPU: the launch bench.py times -- hf_batch_run_period on a batch that DEFERS its phase planes, i.e. the workgroup-staged
-period warp (warp_wg_kernel, csrc/hf_warp_staged.hip) that also builds the plane of its second source -- in the shapes the other
+period warp (warp_wg_kernel, csrc/hf_kernels.hip) that also builds the plane of its second source -- in the shapes the other
 staged-path tests leave out (VERDICT r3 "what's weak" 1-2), every output judged by the pinned oracle or the reference's golden SHA,
 never by another HIP launch:
 

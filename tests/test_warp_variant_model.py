@@ -1,5 +1,6 @@
-"""CPU: the model of the warp's launch selection and of the staged kernel's workgroup bodies (tests/warp_variant_model.py) is pinned to the
-sources, the compiled instantiations are exactly the ones the model can launch plus a stated list of unreachable ones, and the matrix that
+"""CPU: the model of the warp's launch selection (tests/warp_variant_model.py) is compared with the launchers' own plan functions
+(csrc/hf_launch_plan.h, called through tests/launch_plan_probe.cpp) over whole grids of shapes, its model of the staged kernel's workgroup
+bodies is pinned to the device code line by line, the compiled instantiations are exactly the ones the model can launch plus a stated list of unreachable ones, and the matrix that
 tests/test_warp_variants_gpu.py runs against the oracle reaches every launch label in each of modes 0, 1, 2, the generic kernel in modes
 3 to 6, every plane-emission variant and every (element type, plane, workgroup class) pair.  A changed threshold in the launchers or in
 warp_wg_body fails here until the matrix has been reconsidered.
@@ -38,6 +39,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import launch_plan_probe  # noqa: E402
 import warp_variant_model as M  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,84 +61,236 @@ def _once(text, snippet, times=1):
     assert text.count(snippet) == times, (snippet, text.count(snippet))
 
 
-def test_constants_equal_the_sources():
-    kern, kern_h = _src("hf_kernels.hip"), _src("hf_kernels.h")
-    assert _ints(kern, r"constexpr int kWarpTX = (\d+), kWarpTY = (\d+);") == (M.WARP_TX, M.WARP_TY)
-    assert _ints(kern, r"constexpr int kWarpWavesSmall = (\d+), kWarpWavesLarge = (\d+);") == (M.WAVES_SMALL, M.WAVES_LARGE)
-    assert _ints(kern, r"constexpr int kWgWaves = (\d+), kWgRows = (\d+), kWgChunksPerWave = (\d+);") == (M.WG_WAVES, M.WG_ROWS, M.WG_CHUNKS_PER_WAVE)
-    a, b = _ints(kern, r"constexpr long kWgMinWaves = (\d+) \* (\d+);")
-    assert a * b == M.WG_MIN_WAVES
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return launch_plan_probe.load(tmp_path_factory.mktemp("launch_plan_probe"))
+
+
+def test_constants_equal_the_sources(probe):
+    """The constants of hf_launch_plan.h as the compiled header has them; those of the device code by their lines."""
+    k, kern = probe.constants, _src("hf_kernels.hip")
+    assert (k["kWarpTX"], k["kWarpTY"]) == (M.WARP_TX, M.WARP_TY)
+    assert (k["kWarpWavesSmall"], k["kWarpWavesLarge"]) == (M.WAVES_SMALL, M.WAVES_LARGE)
+    assert (k["kWgWaves"], k["kWgRows"], k["kWgChunksPerWave"]) == (M.WG_WAVES, M.WG_ROWS, M.WG_CHUNKS_PER_WAVE)
+    assert k["kWgMinWaves"] == M.WG_MIN_WAVES and k["kWarpRounds"] == M.ROUNDS and k["kSmallFrameBytes"] == M.SMALL_FRAME_BYTES
+    assert (k["kMaxWarpBatch"], k["kMaxWarpOutputs"], k["kMaxFlowBatch"]) == (M.MAX_WARP_BATCH, M.MAX_WARP_OUTPUTS, M.MAX_FLOW_BATCH)
+    assert k["kWarpFastRows"] == M.FAST_ROWS and k["wg_chunks_1"] == M.WG_CHUNKS_PER_WAVE
     assert _ints(kern, r"constexpr int kExtX = (\d+), kExtY = (\d+);") == (M.EXT_X, M.EXT_Y)
     assert _ints(kern, r"constexpr int kWgCells = (\d+);") == (M.WG_CELLS,)
-    assert _ints(kern_h, r"constexpr int kMaxWarpBatch = (\d+);") == (M.MAX_WARP_BATCH,)
-    assert _ints(kern_h, r"constexpr int kMaxWarpOutputs = (\d+);") == (M.MAX_WARP_OUTPUTS,)
-    assert _ints(kern_h, r"constexpr int kMaxFlowBatch = (\d+);") == (M.MAX_FLOW_BATCH,)
     assert _ints(kern, r"constexpr int VEC = 16 / \(int\)sizeof\(E\), NDW = (\d+), CHUNKS = wg_chunks\(NW \* ROWS / 2\), SZ") == (M.NDW,)
-    _once(kern, "const int rows = 2;  // rows per thread")
-    _once(kern, "constexpr int wg_chunks(int nw) { return nw * kWgChunksPerWave; }")
     _once(kern, "constexpr int WR = kWgRows, NW = kWgWaves * 2 / WR;")
     assert M.SMALL_FRAME_BYTES == 1920 * 1088 and M.ROUNDS == 4 * 8192
 
 
 def test_launch_comparisons_equal_the_sources():
-    kern, kern_h, batch, calc = _src("hf_kernels.hip"), _src("hf_kernels.h"), _src("hf_batch.hip"), _src("hf_calc.hip")
-    # the two 1920 x 1088 bounds and the "* 2" one
-    _once(kern, "return (size_t)g.W * g.H * sizeof(E) <= (size_t)1920 * 1088;")
-    _once(kern, "if (cell < VEC || (size_t)g.W * g.H * esz <= (size_t)1920 * 1088) return false;")
-    _once(kern, "const bool small_frame = (size_t)g.W * g.H * sizeof(E) <= (size_t)1920 * 1088 * 2;")
-    assert len(re.findall(r"1920 \* 1088", re.sub(r"//.*", "", kern))) == 3
-    # warp_fast_shape
-    _once(kern, "const int group = cell < VEC ? cell : VEC;", 2)
-    _once(kern, "bool fast = mode >= 0 && mode <= 2 && (g.in_stride % 2) == 0 && (g.out_stride % VEC) == 0 &&")
-    _once(kern, "g.W >= 2 * VEC && group >= 2 && VEC % group == 0 && VEC / group <= 4;")
-    _once(kern, "dw = ((size_t)g.in_stride * sizeof(E)) % 4 == 0 && ((size_t)g.W * sizeof(E)) % 4 == 0 && ((size_t)g.H * g.in_stride * sizeof(E)) % 4 == 0;")
-    _once(kern, "const bool sane = a.white != a.black && a.white != 0.0f && a.white == a.white && a.black == a.black;")
-    _once(kern, "fast = fast && a.mode == mode && (mode != 2 || sane) && a.flow_xy && a.n_out >= 1 && a.n_out <= kMaxWarpOutputs;")
-    _once(kern, "fast = fast && a.s12v[i] >= 0.0f && a.s12v[i] <= 1.0f && (((uintptr_t)a.outv[i]) & (VB - 1)) == 0;")
-    _once(kern, "dw = dw && (((uintptr_t)a.frame12 | (uintptr_t)a.frame21) & 3) == 0;")
-    # launch_warp_fast: outputs per thread, the staged condition, waves per workgroup
-    _once(kern, "const int y_groups = (g.H + rows - 1) / rows, uv_groups = ((g.H >> 1) + rows - 1) / rows;")
-    _once(kern, "const int n_tiles = wpr * ((y_groups + kWarpTY - 1) / kWarpTY + (uv_groups + kWarpTY - 1) / kWarpTY);")
-    _once(kern, "const int out_chunk = small_frame && (long)n_tiles * b.n < 4 * 8192 ? 1 : kMaxWarpOutputs;")
-    _once(kern, "const int n_chunks = (max_out + out_chunk - 1) / out_chunk;")
-    _once(kern, "if constexpr (VB == 16) if (group == VEC && dw && out_chunk > 1 && max_out >= 2 && (long)n_tiles * b.n >= kWgMinWaves &&\n"
-                "                                fastdiv_exact((uint64_t)nb_max * b.n + 8, nb_max)) {")
-    _once(kern_h, "inline bool fastdiv_exact(uint64_t max_u, uint32_t d) { return max_u * d < (1ull << 32); }")
-    _once(kern, "const uint32_t nb_max = (uint32_t)wg_blocks_per_member(wpr, (y_tiles_ + NW - 1) / NW, (uv_tiles_ + NW - 1) / NW, plane_blocks);")
-    _once(kern, "const int plane_blocks = ((g.lw >> 2) * (2 * NW * kWarpTY * WR) + 64 * NW - 1) / (64 * NW);")
-    _once(kern, "return (wpr * 3 + plane_blocks) * wg_super_rows(yb, ub);")
-    _once(kern, "int wg_super_rows(int yb, int ub) { return ub > (yb + 1) / 2 ? ub : (yb + 1) / 2; }")
-    _once(kern, "const int wpb = out_chunk > 1 && (long)n_tiles * n_chunks * b.n >= 4 * 8192 ? warp_max_waves(sizeof(E), group, VB) : kWarpWavesSmall;")
-    _once(kern, "return vb == 16 && group * (int)elem == 16 ? kWarpWavesLarge : kWarpWavesSmall; }")
-    # planes: who gets one, which task builds it, when a batch defers
-    _once(kern, "bool emit = pl && plane_emission_geometry(g, *pl);")
-    _once(kern, "if (!emit || (((uintptr_t)bb.s[m].frame21) & 15) != 0) bb.s[m].plane21 = nullptr;")
-    _once(kern, "return g.rs >= 3 && g.rs <= 4 && pl.rs == g.rs && (lw << g.rs) == g.W && lw == g.lw && (lw & 3) == 0 && pl.mx <= lw && (pl.mx & 3) == 0 &&\n"
-                "           (pl.lwp & 3) == 0 && ((size_t)g.in_stride * esz) % 16 == 0 && ((size_t)g.H * g.in_stride * esz) % 16 == 0 && (g.H & 1) == 0;")
+    """What the launch selection rests on outside hf_launch_plan.h: device code and API-layer control flow, by their lines.  (The selection
+    itself is compared with the model by calling it: the test_plan_* tests below.)"""
+    kern, batch, calc = _src("hf_kernels.hip"), _src("hf_batch.hip"), _src("hf_calc.hip")
     _once(kern, "if (sizeof(E) == 2 && g.rs == 3) plane_fast_task<E, 3, 1>(")
     _once(kern, "else plane_fast_task<E, 4, 1>(")
-    _once(kern, "return n_tiles * per_launch >= kWgMinWaves && g.H == (g.lh << g.rs) && plane_emission_geometry(g, pl);")
-    _once(kern, "const int per_launch = n_members < kMaxWarpBatch ? n_members : kMaxWarpBatch;")
     _once(batch, "b->defer_planes = !l->dual() && !(l->cfg.flags & HF_FLAG_BATCH_EAGER_PLANES) && hf::warp_period_can_build_planes(l->g, l->pl, n);")
     _once(batch, "if (n_out && calculate_flow && b->defer_planes && mode >= 0 && mode <= 2) {")
-    flow = _src("hf_flow.hip")
-    _once(flow, "const int reach = (max_iterations + 1) * 64 + 8;")
-    _once(flow, "pl.mx = (((reach >> g.rs) + 2 + 3) / 4) * 4;")
-    _once(flow, "pl.lwp = ((g.lw + 2 * pl.mx + 4 + 31) / 32) * 32;")
     _once(_src("hf_context.hip"), "const int max_iters = ilog2(ws0);")
-    # launch_warp_fast_any, launch_warp_t, launch_warp_periods, launch_copy_t, one context's period
-    _once(kern, "if (small && launch_warp_fast<E, 8>(g, b, stream, ev0, ev1)) return true;")
-    _once(kern, "return launch_warp_fast<E, 16>(g, b, stream, ev0, ev1, pl, planes_built);")
-    _once(kern, "return (warp_small_frame<E>(g) && warp_fast_shape<E, 8>(g, b, dw)) || warp_fast_shape<E, 16>(g, b, dw);")
-    _once(kern, "const bool aligned = (g.out_stride % VEC) == 0 && (((uintptr_t)a.out) & 15) == 0;")
-    _once(kern, "const bool aligned = (g.in_stride % VEC) == 0 && (g.out_stride % VEC) == 0 &&\n"
-                "                         (((uintptr_t)src | (uintptr_t)out) & 15) == 0;")
-    _once(kern, "for (int first = 0; first < n; first += kMaxWarpBatch) {", 2)
-    _once(kern, "b.n = n - first < kMaxWarpBatch ? n - first : kMaxWarpBatch;")
-    _once(kern, "if (n < 1 || n > kMaxFlowBatch) return false;")
     _once(calc, "const bool fuse = n_out >= 2 && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);")
-    # launch_warp_t passes no counters: a single context's one-output launch is not counted (and is never staged: max_out >= 2)
-    _once(kern, "b.n = 1; b.counters = nullptr; b.s[0] = a;")
+
+
+# ------------------------------------------------------------------------------------------------
+# the model against the launchers' own plan functions (hf_launch_plan.h through tests/launch_plan_probe.cpp)
+# ------------------------------------------------------------------------------------------------
+def max_iters(g):
+    """hf_context.hip: log2 of the initial window, the power of two that covers the grid."""
+    d = max(g.lw, g.lh)
+    return M.ilog2(d if d & (d - 1) == 0 else 1 << d.bit_length())
+
+
+def _up8(v):
+    return -(-v // 8) * 8
+
+
+def plan_label(g, L):
+    if L.family == launch_plan_probe.STAGED:
+        return f"staged.{M.ename(g)}.rs{g.rs}" + (".planes" if L.planes else "")
+    assert L.family == launch_plan_probe.FAST, L
+    return f"fast.{M.ename(g)}.vb{L.vb}.g{L.group}.{'dw' if L.dw else 'nodw'}.{'all' if L.out_chunk > 1 else 'one'}.w{L.waves}"
+
+
+def check_launch_fields(g, L, ms):
+    """The fields of a planned launch that its label does not carry, from the model's tile and block counts."""
+    vec, part = L.vb // M.esize(g), ms[L.first:L.first + L.count]
+    wpr, n_tiles = M.tile_counts(g, vec)
+    max_out = max(m.n_out for m in part)
+    assert L.out_chunk in (1, M.MAX_WARP_OUTPUTS) and L.n_chunks == -(-max_out // L.out_chunk)
+    assert (L.rows, L.y_groups, L.block) == (M.FAST_ROWS, -(-g.H // M.FAST_ROWS), 64 * L.waves)
+    if L.family == launch_plan_probe.STAGED:
+        nw = M.WG_WAVES * 2 // M.WG_ROWS
+        pb = M.plane_blocks(g) if L.planes else 0
+        nb = M.wg_blocks_per_member(g, pb)
+        assert (L.vb, L.group, L.dw, L.waves, L.plane_blocks, L.blocks_per_member, L.wpr) == (16, vec, 1, nw, pb, nb, wpr)
+        assert (L.max_unit, L.grid, L.lds_bytes) == (nb * L.count + 8, _up8(nb * L.count), 2 * (nw * M.WG_ROWS // 2) * M.WG_CHUNKS_PER_WAVE * 16)
+    else:
+        assert L.grid == _up8(-(-n_tiles // L.waves) * L.n_chunks * L.count) and L.planes == 0
+
+
+class Real:
+    """The model's launch functions answered by the plan functions: each checks that the model says the same, then returns the REAL answer, so
+    whatever M.launches / M.labels build on top of them is built from the launchers' own decisions."""
+
+    def __init__(self, probe):
+        self.probe, self.arrays, self.calls = probe, {}, 0
+        self.model = {n: getattr(M, n) for n in ("launch_warp_periods", "launch_warp_t", "launch_copy_t", "defers_planes")}
+
+    def members(self, ms, levels, pending):
+        key = (tuple(ms), levels, None if pending is None else tuple(pending))
+        a = self.arrays.get(key)
+        if a is None:
+            a = self.arrays[key] = launch_plan_probe.members_array(
+                [launch_plan_probe.member(m.n_out, m.ts, m.src_off, m.out_off, levels, wants_plane=bool(pending and pending[i])) for i, m in enumerate(ms)])
+        return a
+
+    def launch_warp_periods(self, g, mode, ms, levels, pending=None):
+        self.calls += 1
+        plan = self.probe.plan_warp(g, mode, self.members(ms, levels, pending), pending is not None, max_iters(g))
+        real = [M.Launch(plan_label(g, L), L.first, L.count, L.family == launch_plan_probe.STAGED,
+                         tuple(L.first + i for i in range(L.count) if L.planes >> i & 1), len(plan) > 1) for L in plan] or None
+        want = self.model["launch_warp_periods"](g, mode, ms, levels, pending)
+        assert real == want, ("plan_warp_periods", g, mode, len(ms), ms[:1], levels, pending is not None, real, want)
+        for L in plan:
+            check_launch_fields(g, L, ms)
+        return real
+
+    def launch_warp_t(self, g, mode, m, levels):
+        self.calls += 1
+        one = M.Member(1, m.ts[:1], m.src_off, m.out_off, m.flow)
+        plan = self.probe.plan_warp(g, mode, self.members([one], levels, None))
+        if plan:
+            check_launch_fields(g, plan[0], [one])
+            real = plan_label(g, plan[0])
+        else:
+            P, vec = self.probe.plan_warp_generic(g, m.out_off), 16 // M.esize(g)
+            assert (P.grid_x, P.grid_y, P.block) == (-(-g.W // (64 * vec)), (g.H + (g.H >> 1) + 3) // 4, 256)
+            real = f"generic.{M.ename(g)}.{'aligned' if P.aligned else 'unaligned'}"
+        want = self.model["launch_warp_t"](g, mode, m, levels)
+        assert real == want, ("launch_warp", g, mode, m, levels, real, want)
+        return real
+
+    def launch_copy_t(self, g, m):
+        self.calls += 1
+        P, vec = self.probe.plan_copy(g, m.src_off, m.out_off), 16 // M.esize(g)
+        assert (P.grid_x, P.grid_y, P.block) == (-(-g.W // (64 * vec)), (g.H + (g.H >> 1) + 3) // 4, 256)
+        real, want = f"copy.{M.ename(g)}.{'aligned' if P.aligned else 'unaligned'}", self.model["launch_copy_t"](g, m)
+        assert real == want, ("plan_copy", g, m, real, want)
+        return real
+
+    def defers_planes(self, g, n_members):
+        self.calls += 1
+        real, want = self.probe.can_build_planes(g, max_iters(g), n_members), self.model["defers_planes"](g, n_members)
+        assert real == want, ("warp_period_can_build_planes", g, n_members, real, want)
+        return real
+
+
+@pytest.fixture
+def real(probe, monkeypatch):
+    r = Real(probe)
+    for name in r.model:
+        monkeypatch.setattr(M, name, getattr(r, name))
+    return r
+
+
+def test_plan_equals_the_model_over_the_sweep(real):
+    """Every shape of sweep_labels() in modes 0 to 3: the plan functions decide what the model decides, field by field, and so produce
+    exactly the declared labels and no other."""
+    seen = sweep_labels()
+    assert real.calls > 4 * 105600
+    for mode in (0, 1, 2):
+        assert seen[mode] == M.MODE_LABELS | M.COPY_LABELS, (mode, sorted(seen[mode] ^ (M.MODE_LABELS | M.COPY_LABELS)))
+    assert seen[3] == M.GENERIC_LABELS | M.COPY_LABELS, sorted(seen[3])
+
+
+def test_plan_equals_the_model_on_the_matrix(real):
+    """Every case of the matrix in each of its modes, ahead of the chain and not."""
+    seen = set()
+    for c in M.CASES:
+        for mode in c.modes:
+            seen |= M.labels(c, mode)
+            for ahead in (False, True):
+                if c.path in ("batch", "period"):
+                    M.launches(c, mode, ahead_of_chain=ahead)
+    assert seen == M.MODE_LABELS | M.COPY_LABELS and real.calls > len(M.CASES)
+
+
+SWEEP_SIZES = [(180, 320), (360, 640), (720, 1280), (1080, 1920), (1088, 1536), (1088, 2816), (1440, 2560), (2160, 3840), (4320, 7680), (722, 1282)]
+
+
+def test_deferral_and_phase_layout_equal_the_plan(probe, real):
+    """defers_planes against warp_period_can_build_planes and phase_layout against make_phase_layout on the sweep's geometries."""
+    deferring = 0
+    for hdr in (0, 1):
+        for H, W in SWEEP_SIZES:
+            for mr in (67, 135, 270, 540, 1080, 4320):
+                for si in (0, W + 2, W + 8, W + 64):
+                    g = M.geometry(M._c("s", hdr, H, W, mr, si=si))
+                    pl = probe.phase_layout(g, max_iters(g))
+                    nph = 1 << g.rs
+                    assert (pl.mx, pl.lwp) == M.phase_layout(g) and (pl.rs, pl.nph, pl.nph2) == (g.rs, nph, max(1, nph // 2)), g
+                    assert pl.bytes == g.H * pl.nph2 * pl.lwp * 4
+                    deferring += sum(real.defers_planes(g, n) for n in (0, 1, 2, 3, 4, 10, 11, 15, 16, 17, 32))
+    assert deferring > 50
+
+
+def _both_sides(real, c, modes=(0, 1, 2)):
+    """The labels of a case per mode, from the plan (compared with the model on the way)."""
+    return [M.labels(c, m) for m in modes]
+
+
+def test_plan_on_both_sides_of_each_threshold(probe, real):
+    P, g1080 = launch_plan_probe, M.geometry(M._c("x", 1, 1080, 1920, 135))
+    # 10 and 11 members of 1080p HDR at rs 3
+    assert _both_sides(real, M._c("x", 1, 1080, 1920, 135, 10)) == [{"fast.u16.vb16.g8.dw.one.w4"}] * 3
+    assert _both_sides(real, M._c("x", 1, 1080, 1920, 135, 11)) == [{"staged.u16.rs3"}] * 3
+    # frames of exactly 1920 x 1088 bytes (8-byte threads) and exactly twice that (the last size with one output per thread), and just above
+    assert _both_sides(real, M._c("x", 0, 1088, 1920, 272, 1, path="single")) == [{"fast.u8.vb8.g4.dw.one.w4"}] * 3
+    assert _both_sides(real, M._c("x", 0, 1090, 1920, 272, 1, path="single")) == [{"fast.u8.vb16.g4.dw.one.w4"}] * 3
+    assert _both_sides(real, M._c("x", 1, 1088, 1920, 272, 1, path="single")) == [{"fast.u16.vb16.g4.dw.one.w4"}] * 3
+    assert _both_sides(real, M._c("x", 1, 1090, 1920, 272, 1, path="single")) == [{"fast.u16.vb16.g4.dw.all.w4"}] * 3
+    assert not real.defers_planes(M.geometry(M._c("x", 0, 1088, 1920, 136)), 16)
+    # 16 and 17, 32 and 33, 0 members
+    for n, want in ((16, 1), (17, 2), (32, 2), (33, 0), (0, 0)):
+        ms = [M.Member(2, (0.0, 1.0), 0, 0, "uniform:9:-5")] * n
+        r = real.launch_warp_periods(g1080, 2, ms, (0.0, 255.0))
+        assert len(r or []) == want and (not r or [ln.count for ln in r] == [min(16, n), n - 16][:want]), (n, r)
+    # n_out 0, 1, 6, 7 -- one member out of range and nothing at all is launched, whichever part it is in
+    for n_out, ok in ((0, False), (1, True), (6, True), (7, False)):
+        for at in (0, 20):
+            ms = [M.Member(2, (0.0, 1.0), 0, 0, "uniform:9:-5")] * 21
+            ms[at] = M.Member(n_out, M.T6[:min(n_out, 6)], 0, 0, "uniform:9:-5")
+            assert (real.launch_warp_periods(g1080, 2, ms, (0.0, 255.0)) is not None) == ok, (n_out, at)
+    # a blend scalar outside [0, 1]; a member without packed flow
+    for ts, ok in (((0.0, 1.0), True), ((-0.001, 1.0), False), ((0.0, 1.001), False)):
+        assert (real.launch_warp_periods(g1080, 2, [M.Member(2, ts, 0, 0, "uniform:9:-5")], (0.0, 255.0)) is not None) == ok, ts
+    assert probe.plan_warp(g1080, 2, [P.member(2, (0.0, 1.0))]) and not probe.plan_warp(g1080, 2, [P.member(2, (0.0, 1.0), has_flow_xy=False)])
+    # mode 2 with levels the blend cannot take: white == black, white == 0, NaN -- modes 0 and 1 do not look at them
+    for levels in ((16.0, 16.0), (-5.0, 0.0), (0.0, float("nan")), (float("nan"), 255.0)):
+        lb = _both_sides(real, M._c("x", 1, 1080, 1920, 135, 3, levels=levels))
+        assert lb[0] == lb[1] == {"fast.u16.vb16.g8.dw.one.w4"} and lb[2] == {"generic.u16.aligned"}, (levels, lb)
+    # dw is decided per part: only the second launch of 20 members has a source at base + 2
+    ms = [M.Member(2, (0.0, 1.0), 0, 0, "uniform:9:-5")] * 19 + [M.Member(2, (0.0, 1.0), 2, 0, "uniform:9:-5")]
+    assert [ln.label for ln in real.launch_warp_periods(g1080, 0, ms, (0.0, 255.0))] == ["staged.u16.rs3", "fast.u16.vb16.g8.nodw.one.w4"]
+    # a small frame whose outputs are 8- but not 16-byte aligned takes 8-byte threads; at rs 0 neither 8- nor 16-byte threads hold a cell pair
+    assert _both_sides(real, M._c("x", 0, 180, 320, 67, 2, out=(8,))) == [{"fast.u8.vb8.g4.dw.one.w4"}] * 3
+    assert _both_sides(real, M._c("x", 0, 180, 320, 270, 2, out=(8,))) == [{"generic.u8.unaligned"}] * 3
+    # planes: asked for without a layout, with one, with a frame21 that is not 16-byte aligned
+    g2160, two = M.geometry(M._c("x", 1, 2160, 3840, 270)), (0.0, 1.0)
+    for have_pl, wants, off21, planes in ((False, True, 0, 0), (True, False, 0, 0), (True, True, 0, 0b1111), (True, True, 8, 0b0111)):
+        ms = [P.member(2, two, wants_plane=wants) for _ in range(3)] + [P.member(2, two, wants_plane=wants, src21_off=off21)]
+        (L,) = probe.plan_warp(g2160, 2, ms, have_pl, max_iters(g2160))
+        assert (L.family, L.planes, L.plane_blocks) == (P.STAGED, planes, M.plane_blocks(g2160) if planes else 0), (have_pl, wants, off21, L)
+    # one 8K-class shape on each side of fastdiv_exact: (blocks per member x members + 8) x blocks per member against 2^32
+    for n, staged in ((12, True), (13, False)):       # 5760 x 7680 HDR at rs 4: 18,900 workgroups a member
+        c = M._c("x", 1, 5760, 7680, 360, n, (2,))
+        g = M.geometry(c)
+        nb = M.wg_blocks_per_member(g, M.plane_blocks(g))
+        assert probe.fastdiv_exact(nb * n + 8, nb) == ((nb * n + 8) * nb < 1 << 32) == staged, (n, nb)
+        assert _both_sides(real, c) == [{"staged.u16.rs4" if staged else "fast.u16.vb16.g8.dw.all.w16"}] * 3, n
 
 
 def test_workgroup_decision_equals_the_sources():
@@ -224,7 +378,7 @@ def compiled_instantiations():
 
 def sweep_labels():
     """Every label the model produces over sizes 180p .. 4320p, max_res 67 .. 4320, strides, alignments, 1 .. 32 members, 1 .. 6 outputs."""
-    sizes = [(180, 320), (360, 640), (720, 1280), (1080, 1920), (1088, 1536), (1088, 2816), (1440, 2560), (2160, 3840), (4320, 7680), (722, 1282)]
+    sizes = SWEEP_SIZES
     seen = {m: set() for m in (0, 1, 2, 3)}
     for hdr in (0, 1):
         for H, W in sizes:

@@ -1,11 +1,12 @@
-"""CPU model of which warp kernel a launch runs and which body every workgroup of the staged kernel takes (csrc/hf_kernels.hip
-warp_fast_shape, warp_small_frame, launch_warp_fast, launch_warp_fast_any, launch_warp_t, launch_warp_periods,
-warp_period_can_build_planes, plane_emission_geometry, launch_copy_t, warp_wg_body).  numpy only.
+"""CPU model of which warp kernel a launch runs and which body every workgroup of the staged kernel takes (csrc/hf_launch_plan.h
+plan_warp_periods, plan_warp_launch, warp_fast_shape, plan_warp_generic, plan_copy, warp_period_can_build_planes, plane_emission_geometry;
+csrc/hf_kernels.hip launch_warp, launch_warp_periods, warp_wg_body).  numpy only.
 
 The launchers choose by element type, resolution scalar, frame bytes, strides, pointer alignment, batch size, outputs per period and mode;
 inside warp_wg_kernel every workgroup then stages a window (interior, or mirror-extended at a frame edge), takes the interior global path
 or the generic body.  All three bodies give the same pixels, so only this model and the device counters can tell that the staged body ran.
-tests/test_warp_variant_model.py pins every constant and comparison restated here to the sources and proves that CASES -- the matrix
+The launch selection restated here is compared with the launchers' plan functions by tests/test_warp_variant_model.py (every shape of its
+sweep, field by field), which pins the workgroup decision to the device code and proves that CASES -- the matrix
 tests/test_warp_variants_gpu.py runs against the oracle -- reaches every label and every workgroup class the model knows.
 
 Launch labels
@@ -31,7 +32,7 @@ import collections
 
 import numpy as np
 
-# constants of csrc/hf_kernels.hip and hf_kernels.h (pinned by tests/test_warp_variant_model.py)
+# constants of csrc/hf_launch_plan.h and hf_kernels.hip (compared with the launchers' plan functions by tests/test_warp_variant_model.py)
 WARP_TX, WARP_TY = 16, 4                  # kWarpTX, kWarpTY
 WAVES_SMALL, WAVES_LARGE = 4, 16          # kWarpWavesSmall, kWarpWavesLarge
 WG_WAVES, WG_ROWS, WG_CHUNKS_PER_WAVE = 4, 2, 192
