@@ -13,6 +13,8 @@ Two partitions are offered:
   * shard_timeline:  one long clip cut into contiguous chunks; chunk g needs the frames before its first period
                      as overlap (ring N-2, N-1, N + previous flow = 3, + 12 periods of delta history when the
                      scene-change detector is on); run_chunk() executes one chunk with the native protocol state
+  * run_clips:       whole clips through ONE batch on one GPU, a clip per member, the warp-or-copy decision taken on the
+                     device (hf_batch_run_period_auto): no host wait per period, one sync at the end
 Results are gathered in index order by the caller (rank-local lists; torch.distributed only for the
 barrier/timing in bench.py).
 """
@@ -92,4 +94,45 @@ def run_chunk(calc, chunk: TimelineChunk, frames, frame_output=2, scene_change_t
                 calc.copyFrame(); kinds.append("copy")
             outs.append(calc.downloadFrame().copy())
     host.close()
+    return outs, kinds
+
+
+SCENE_RECORD_RING = 128   # periods of records a batch member holds between two reads (hf_batch_scene_read)
+
+
+def run_clips(batch, clips, source_frame_time=SOURCE_24, target_frame_time=TARGET_60, frame_output=2, threshold=None):
+    """Whole clips through a batch, one clip per member in lockstep, with the filter's scene-change decision taken on the
+    device (FlowBatch.runPeriodAuto): nothing waits per period, one sync at the end (clips longer than the record ring:
+    one more per 128 periods, to hand the records out).
+
+    batch: a FlowBatch whose leader was created with HF_FLAG_BATCH_EAGER_PLANES (runPeriodAuto refuses a batch that defers
+    its phase planes); every member starts its clip here (m_frameCount is zeroed, the history re-armed).
+    clips[i]: member i's source frames as device pointers (NV12 / P010 frames in device memory), all clips of one
+    length; a frame must stay untouched until three further periods have been issued (the ring references it).
+    Returns (outputs, kinds): outputs[i] = the clip's output frames in order as DeviceBuffer objects (the caller frees them),
+    kinds[i] = "warp" | "copy" per output frame, from the device's records."""
+    from .calc import DeviceBuffer
+    n = len(batch.members)
+    if len(clips) != n or len({len(c) for c in clips}) != 1:
+        raise ValueError("run_clips: one clip per member, all of one length")
+    plan = BlendSchedule(source_frame_time, target_frame_time).plan(len(clips[0]))
+    for i, m in enumerate(batch.members):
+        m.m_frameCount = 0                                    # NewSegment (HopperRender.cpp:840)
+        batch.sceneSet(i, source_frame_time, -1 if threshold is None else threshold)
+    outs, period_kinds = [[] for _ in range(n)], [[] for _ in range(n)]
+
+    def collect():
+        batch.sync()
+        for i in range(n):
+            period_kinds[i] += [r["kind"] for r in batch.sceneRead(i)]
+
+    for k, ts in enumerate(plan):
+        if k and k % SCENE_RECORD_RING == 0:
+            collect()
+        bufs = [[DeviceBuffer(m.output_frame_bytes, m.device_index) for _ in ts] for m in batch.members]
+        batch.runPeriodAuto([c[k] for c in clips], [ts] * n, [[b.ptr for b in row] for row in bufs], frame_output)
+        for i in range(n):
+            outs[i] += bufs[i]
+    collect()
+    kinds = [[("warp" if kind else "copy") for kind, ts in zip(period_kinds[i], plan) for _ in ts] for i in range(n)]
     return outs, kinds

@@ -381,6 +381,30 @@ class FlowBatch:
         if rc != 0:
             self._check(rc)
 
+    def sceneSet(self, member, source_frame_time, threshold=-1):
+        """hf_batch_scene_set: arms / re-arms member's scene-change history (NewSegment); threshold < 0 = DEFAULT_SCENE_CHANGE_THRESHOLD."""
+        self._check(self._lib.hf_batch_scene_set(self._b, int(member), int(source_frame_time), int(threshold)))
+
+    def runPeriodAuto(self, dev_ptrs, scalars, out_ptrs, mode=BlendedFrame, force_kind=None):
+        """hf_batch_run_period_auto: one source period of every member, warp or copy decided on the device; only enqueues.
+        scalars[i] / out_ptrs[i]: member i's lists (an empty list: no output); force_kind: None or per member -1 decide / 0 copy / 1 warp."""
+        frames, _, counts, t, outs, mode = self.preparePeriod(dev_ptrs, scalars, out_ptrs, mode)
+        force = (C.c_int32 * len(self.members))(*[int(k) for k in force_kind]) if force_kind is not None else None
+        rc = self._lib.hf_batch_run_period_auto(self._b, frames, counts, t, outs, mode, force)
+        if rc != 0:
+            self._check(rc)
+
+    def sceneRead(self, member):
+        """hf_batch_scene_read (after sync()): member's records since the last read, in period order, as dicts of
+        frame_count, total_delta, kind (1 warp / 0 copy), average, d1, d2."""
+        n = C.c_int(0)
+        self._check(self._lib.hf_batch_scene_read(self._b, int(member), None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        recs = (capi.HfSceneRecord * n.value)()
+        self._check(self._lib.hf_batch_scene_read(self._b, int(member), recs, n.value, C.byref(n)))
+        return [{k: getattr(r, k) for k, _ in r._fields_} for r in recs[:n.value]]
+
     def sync(self):
         self._check(self._lib.hf_batch_sync(self._b))
 

@@ -75,6 +75,11 @@ class HfTimelineRecord(C.Structure):
                 ("duration_ms", C.c_double)]
 
 
+class HfSceneRecord(C.Structure):
+    _fields_ = [("frame_count", C.c_uint32), ("total_delta", C.c_uint32), ("kind", C.c_int32), ("average", C.c_int32), ("d1", C.c_int32),
+                ("d2", C.c_int32)]
+
+
 class HfDebugCounters(C.Structure):
     _fields_ = [("warp_workgroups", C.c_uint32 * 3), ("reserved", C.c_uint32), ("level_windows", (C.c_uint32 * 2) * 16),
                 ("level_reused", (C.c_uint32 * 2) * 16), ("level_window_size", C.c_int32 * 16)]
@@ -132,6 +137,9 @@ SIGNATURES = {
     "hf_batch_interpolate_period": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i]),
     "hf_batch_run_period": (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i]),
     "hf_batch_defers_planes": (_i, [_vp]),
+    "hf_batch_scene_set": (_i, [_vp, _i, C.c_int64, C.c_int32]),
+    "hf_batch_run_period_auto": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i, C.POINTER(C.c_int32)]),
+    "hf_batch_scene_read": (_i, [_vp, _i, C.POINTER(HfSceneRecord), _i, C.POINTER(_i)]),
     "hf_batch_sync": (_i, [_vp]),
     "hf_batch_size": (_i, [_vp]),
     "hf_batch_timeline_enable": (_i, [_vp, _i, _i]),

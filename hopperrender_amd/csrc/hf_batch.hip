@@ -114,6 +114,25 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
     return HF_OK;
 }
 
+namespace {
+// timeline on: every launch of a period call carries its own start / stop events (hf_kernels.h HF_LAUNCH)
+struct ObserverGuard {
+    hf_batch* b;
+    explicit ObserverGuard(hf_batch* x) : b(nullptr) {
+        if (!x->tl.active) return;
+        if (x->tl.skip > 0) { x->tl.skip--; return; }      // armed, not recording yet
+        b = x;
+        hf::t_launch_observer = &b->tl;
+    }
+    ~ObserverGuard() {
+        if (!b) return;
+        hf::t_launch_observer = nullptr;
+        b->tl.period++;
+        if (b->tl.recs.size() + 32 > b->tl.capacity) b->tl.active = false;   // no room for another whole period: back to graph replays
+    }
+};
+}  // namespace
+
 }  // namespace hfi
 
 extern "C" {
@@ -220,12 +239,22 @@ void hf_batch_destroy(hf_batch* b) {
     for (hipStream_t ws : b->warp_streams) hipStreamDestroy(ws);
     if (b->stream) hipStreamDestroy(b->stream);
     for (hipEvent_t e : b->tl.events) hipEventDestroy(e);
+    if (b->scene_states) hipFree(b->scene_states);
+    if (b->scene_kinds) hipFree(b->scene_kinds);
+    if (b->scene_records) hipHostFree(b->scene_records);
     delete b;
 }
 
 int hf_batch_update_frames_device_ref(hf_batch* b, const void* const* device_frames) { return batch_update(b, device_frames, false); }
 
-int hf_batch_calculate_optical_flow(hf_batch* b) {
+}  // extern "C"
+
+namespace hfi {
+
+// hf_batch_calculate_optical_flow.  warmup_keeps_flow (hf_batch_run_period_auto): a member whose m_frameCount is below 3 rides the batched
+// launches -- its ring always holds valid buffers -- but the filter would not have calculated a flow for it (HopperRender.cpp:955), so its
+// chain writes the buffer the next real chain overwrites and nothing else of the member moves: no flow-buffer swap, no timing, no delta.
+int batch_calculate(hf_batch* b, bool warmup_keeps_flow) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     hf_ctx* l = b->members[0];
     const int n = (int)b->members.size();
@@ -242,7 +271,8 @@ int hf_batch_calculate_optical_flow(hf_batch* b) {
         // timeline: the chain's launches one by one, each with the events of its own dispatch (a graph replay has no per-node timestamps)
         if (int rc = enqueue_flow_chain(b->members.data(), n, b->stream)) return batch_fail(b, rc, l->err);
         for (hf_ctx* m : b->members)
-            if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
+            if (!(warmup_keeps_flow && m->p.frame_count < 3))
+                if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
         return HF_OK;
     }
     auto it = b->graphs.find(key);
@@ -269,9 +299,16 @@ int hf_batch_calculate_optical_flow(hf_batch* b) {
     span_end(l, span);
     if (span >= 0) l->spans[span].frames = n;
     for (hf_ctx* m : b->members)
-        if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
+        if (!(warmup_keeps_flow && m->p.frame_count < 3))
+            if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
     return HF_OK;
 }
+
+}  // namespace hfi
+
+extern "C" {
+
+int hf_batch_calculate_optical_flow(hf_batch* b) { return batch_calculate(b, false); }
 
 int hf_batch_size(const hf_batch* b) { return b ? (int)b->members.size() : 0; }
 
@@ -282,21 +319,7 @@ int hf_batch_interpolate_period(hf_batch* b, const int* n_out, const float* t, v
 int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calculate_flow, const int* n_out, const float* t,
                         void* const* device_out, int mode) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
-    struct ObserverGuard {   // timeline on: every launch of this call carries its own start / stop events (hf_kernels.h HF_LAUNCH)
-        hf_batch* b;
-        explicit ObserverGuard(hf_batch* x) : b(nullptr) {
-            if (!x->tl.active) return;
-            if (x->tl.skip > 0) { x->tl.skip--; return; }      // armed, not recording yet
-            b = x;
-            hf::t_launch_observer = &b->tl;
-        }
-        ~ObserverGuard() {
-            if (!b) return;
-            hf::t_launch_observer = nullptr;
-            b->tl.period++;
-            if (b->tl.recs.size() + 32 > b->tl.capacity) b->tl.active = false;   // no room for another whole period: back to graph replays
-        }
-    } observer_guard(b);
+    ObserverGuard observer_guard(b);
     if (device_frames) if (int rc = batch_update(b, device_frames, b->defer_planes)) return rc;
     // Deferred phase planes: a period whose older frame still lacks its full plane issues its warps FIRST (they do not depend on
     // this period's chain) and lets that launch build the plane; same results as the order of the three calls.
@@ -405,6 +428,131 @@ int hf_batch_sync(hf_batch* b) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     for (hf_ctx* m : b->members)
         if (int rc = hf_sync(m)) return batch_fail(b, rc, m->err);
+    return HF_OK;
+}
+
+// ---- whole clips through a batch: warp or copy per member and period, decided on the device (hf_scene.hip) ----
+int hf_batch_scene_set(hf_batch* b, int member, int64_t source_frame_time, int32_t threshold) {
+    if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
+    const int n = (int)b->members.size();
+    if (member < 0 || member >= n) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_scene_set: member outside [0, batch size)");
+    hf_ctx* l = b->members[0];
+    if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
+    if (!b->scene_records) {   // first use: the members' histories and kinds on the device, their record rings in mapped host memory
+        const size_t nrec = (size_t)hf::kMaxFlowBatch * hf_batch::kSceneRing;
+        hf::SceneState* st = nullptr;
+        int32_t* kinds = nullptr;
+        hf::SceneRecord* recs = nullptr, *recs_dev = nullptr;
+        const bool ok = hipMalloc((void**)&st, hf::kMaxFlowBatch * sizeof(hf::SceneState)) == hipSuccess &&
+                        hipMalloc((void**)&kinds, hf::kMaxFlowBatch * sizeof(int32_t)) == hipSuccess &&
+                        hipHostMalloc((void**)&recs, nrec * sizeof(hf::SceneRecord), hipHostMallocMapped) == hipSuccess &&
+                        hipHostGetDevicePointer((void**)&recs_dev, recs, 0) == hipSuccess &&
+                        hipMemsetAsync(st, 0, hf::kMaxFlowBatch * sizeof(hf::SceneState), b->stream) == hipSuccess &&
+                        hipMemsetAsync(kinds, 0, hf::kMaxFlowBatch * sizeof(int32_t), b->stream) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (st) hipFree(st);
+            if (kinds) hipFree(kinds);
+            if (recs) hipHostFree(recs);
+            return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "hf_batch_scene_set: cannot allocate the scene-change state");
+        }
+        std::memset(recs, 0, nrec * sizeof(hf::SceneRecord));
+        b->scene_states = st; b->scene_kinds = kinds; b->scene_records = recs; b->scene_records_dev = recs_dev;
+        b->scene.assign((size_t)n, hf_batch::SceneMember{});
+    }
+    hf_batch::SceneMember& sm = b->scene[(size_t)member];
+    sm.armed = true;
+    sm.clear = true;   // NewSegment: the next scene_decide launch starts the member's history over (stream order, nothing to wait for)
+    sm.cap = hf::scene_history_cap(source_frame_time > 0 ? source_frame_time : 417083);   // hf_filter_create's default
+    sm.threshold = (uint32_t)(threshold < 0 ? DEFAULT_SCENE_CHANGE_THRESHOLD : threshold);
+    return HF_OK;
+}
+
+int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, const int* n_out, const float* t, void* const* device_out,
+                             int mode, const int32_t* force_kind) {
+    if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
+    hf_ctx* l = b->members[0];
+    const int n = (int)b->members.size();
+    // everything that can be refused is refused before anything is enqueued
+    if (!device_frames || !n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null argument");
+    if (mode < 0 || mode > 6) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode outside [0, 6]");
+    if (b->defer_planes)
+        return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: this batch defers its phase planes, so a period's warps are issued ahead of its chain and the "
+                                           "decision does not exist yet; create the leader with HF_FLAG_BATCH_EAGER_PLANES");
+    if (l->dual())
+        return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: HF_FLAG_DUAL_STREAM members warp on streams of their own, beside the chain that decides; "
+                                           "create the members without HF_FLAG_DUAL_STREAM");
+    for (int m = 0; m < n; m++) {
+        if (!device_frames[m]) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null frame");
+        if (b->members[m]->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: a member uses asynchronous host I/O");
+        if (n_out[m] < 0 || n_out[m] > HF_MAX_PERIOD_OUTPUTS) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: n_out outside [0, 6]");
+        for (int i = 0; i < n_out[m]; i++)
+            if (t[m * HF_MAX_PERIOD_OUTPUTS + i] > 1.0f)
+                return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");
+        if (force_kind && (force_kind[m] < -1 || force_kind[m] > 1))
+            return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: force_kind outside {-1, 0, 1}");
+        if (b->scene.empty() || !b->scene[(size_t)m].armed)
+            return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: member " + std::to_string(m) + " was never armed; call hf_batch_scene_set for every member first");
+        if (b->scene[(size_t)m].written - b->scene[(size_t)m].read >= hf_batch::kSceneRing)
+            return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: the record ring of member " + std::to_string(m) + " is full (" +
+                                               std::to_string(hf_batch::kSceneRing) + " periods); call hf_batch_sync and hf_batch_scene_read more often");
+    }
+    if (int rc = batch_check_flow_params(b)) return rc;
+    ObserverGuard observer_guard(b);
+    if (int rc = batch_update(b, device_frames, false)) return rc;
+    if (int rc = batch_calculate(b, true)) return rc;
+    // the decision, behind the chain's last launch
+    hf::SceneDecideArgs da{};
+    hf::SceneCopyArgs ca{};
+    da.n = ca.n = n;
+    for (int m = 0; m < n; m++) {
+        hf_ctx* c = b->members[m];
+        hf_batch::SceneMember& sm = b->scene[(size_t)m];
+        const uint32_t fc = c->p.frame_count;   // m_frameCount of this period (the update has counted the new frame)
+        da.total_delta[m] = c->d_total_delta;
+        da.frame_count[m] = fc;
+        da.threshold[m] = sm.threshold;
+        da.slot[m] = (uint32_t)(sm.written % hf_batch::kSceneRing);
+        da.cap[m] = (int8_t)sm.cap;
+        da.push[m] = fc >= 3 ? 1 : 0;           // HopperRender.cpp:955-972
+        da.clear[m] = sm.clear ? 1 : 0;
+        da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
+        hf::SceneCopyArgs::Member& cm = ca.m[m];
+        const float scale = c->g.hdr ? 256.0f : 1.0f;   // opticalFlowCalcHDR.cpp:173-174
+        cm.src = c->ring[fc >= 3 ? 0 : fc >= 2 ? 1 : 2];   // opticalFlowCalcSDR.cpp:173
+        cm.n_out = n_out[m];
+        for (int i = 0; i < n_out[m]; i++) {
+            void* o = device_out[m * HF_MAX_PERIOD_OUTPUTS + i];
+            cm.outs[i] = o ? o : c->out_frame;
+        }
+        cm.black = c->p.black_level * scale; cm.white = c->p.white_level * scale;
+    }
+    hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
+    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
+    for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
+    // the unchanged warps of the period (diagnostic modes and n_out == 0: member by member on the same stream), then the repair of the cut periods
+    if (int rc = hf_batch_interpolate_period(b, n_out, t, device_out, mode)) return rc;
+    hf::launch_scene_copy(l->g, ca, b->scene_kinds, b->stream);
+    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_copy launch failed");
+    return HF_OK;
+}
+
+int hf_batch_scene_read(hf_batch* b, int member, hf_scene_record* out, int capacity, int* n_records) {
+    if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
+    if (!n_records || capacity < 0 || (capacity > 0 && !out)) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_scene_read: bad argument");
+    if (member < 0 || member >= (int)b->members.size()) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_scene_read: member outside [0, batch size)");
+    *n_records = 0;
+    if (b->scene.empty()) return HF_OK;
+    if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamSynchronize(b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");   // (a no-op after hf_batch_sync)
+    hf_batch::SceneMember& sm = b->scene[(size_t)member];
+    const uint64_t have = sm.written - sm.read;
+    *n_records = (int)have;   // how many there were; min(capacity, that) are handed out and leave the ring
+    static_assert(sizeof(hf_scene_record) == sizeof(hf::SceneRecord), "hf_scene_record is hf::SceneRecord");
+    const uint64_t k = have < (uint64_t)capacity ? have : (uint64_t)capacity;
+    for (uint64_t i = 0; i < k; i++)
+        std::memcpy(&out[i], &b->scene_records[(size_t)member * hf_batch::kSceneRing + (size_t)((sm.read + i) % hf_batch::kSceneRing)], sizeof(hf_scene_record));
+    sm.read += k;
     return HF_OK;
 }
 

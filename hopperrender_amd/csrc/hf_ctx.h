@@ -4,7 +4,8 @@
 //                    statistics, profiling spans, parity taps, device-memory helpers
 //   hf_calc.hip      the five virtuals of one context: updateFrame, calculateOpticalFlow (the refinement chain as a cached hipGraph), warpFrames,
 //                    copyFrame, downloadFrame, and the fused period calls
-//   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers)
+//   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
+//                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
 //   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async / hf_download_frame_async, hf_wait_*)
 //
 // Host orchestration restated from the reference's opticalFlowCalcSDR.cpp / opticalFlowCalcHDR.cpp (cited per function); the
@@ -37,6 +38,7 @@
 #include "../../include/hopperflow.h"
 #include "../../include/hopperflow_diag.h"
 #include "hf_kernels.h"
+#include "hf_scene.h"
 
 namespace hfi {
 
@@ -182,6 +184,18 @@ struct hf_batch {
     hipStream_t stream = nullptr;           // = members[0]'s stream, shared by all members while the batch exists
     std::map<std::vector<int>, hipGraphExec_t> graphs;
     bool defer_planes = false;              // hf_batch_run_period: grid samples at update, full plane of frame N-1 from the warp launch
+    // hf_batch_run_period_auto (hf_scene.hip): allocated by the first hf_batch_scene_set
+    static constexpr uint32_t kSceneRing = 128;          // records a member can hold between two hf_batch_scene_read calls
+    struct SceneMember {
+        bool armed = false, clear = false;  // clear: (re-)armed since its last period -- the next scene_decide launch starts its history over
+        int cap = 0;                        // hf::scene_history_cap(source_frame_time)
+        uint32_t threshold = 0;
+        uint64_t written = 0, read = 0;     // records appended / handed out so far (slot = index % kSceneRing)
+    };
+    std::vector<SceneMember> scene;
+    hf::SceneState* scene_states = nullptr; // device [kMaxFlowBatch]
+    int32_t* scene_kinds = nullptr;         // device [kMaxFlowBatch]: 1 warp / 0 copy of the period in flight
+    hf::SceneRecord* scene_records = nullptr, *scene_records_dev = nullptr;   // mapped host memory [kMaxFlowBatch][kSceneRing] and its device view
     std::string err;
 };
 
@@ -220,6 +234,7 @@ int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind);
 int batch_fail(hf_batch* b, int code, const std::string& msg);
 int batch_update(hf_batch* b, const void* const* device_frames, bool defer);
 int batch_check_flow_params(hf_batch* b);
+int batch_calculate(hf_batch* b, bool warmup_keeps_flow);
 int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched);
 
 // hf_async_io.hip

@@ -183,6 +183,40 @@ void launch_copy(const Geom& g, const void* src, void* out, float black, float w
 void launch_planar_in(int hdr, int H, int stride, const void* planar, void* semi, hipStream_t stream);
 void launch_planar_out(int hdr, int H, int stride, const void* semi, void* planar, hipStream_t stream);
 bool dbg_bounds_read_planar(unsigned out[5], bool reset);
+// Scene-cut copy periods of a batch, decided on the device (hf_scene.hip; hf_batch_run_period_auto).  One record per member and period:
+// the layout of hf_scene_record (include/hopperflow.h).
+struct SceneRecord {
+    uint32_t frame_count, total_delta;
+    int32_t kind, average, d1, d2;
+};
+struct SceneState;   // hf_scene.h
+// scene_decide: one thread per member, behind the chain's last launch.  A member with push set reads *total_delta once and pushes it
+// (scene_push, hf_scene.h); every member gets kinds[m] = 1 warp / 0 copy and one record at records[m * ring + slot[m]] (mapped host memory).
+struct SceneDecideArgs {
+    int n;
+    const uint32_t* total_delta[kMaxFlowBatch];   // FlowStep::total_delta of the member (mapped host memory the chain published to)
+    uint32_t frame_count[kMaxFlowBatch];          // m_frameCount of the period
+    uint32_t threshold[kMaxFlowBatch];
+    uint32_t slot[kMaxFlowBatch];                 // record slot of this period in the member's ring
+    int8_t cap[kMaxFlowBatch];                    // scene_history_cap of the member
+    int8_t push[kMaxFlowBatch];                   // m_frameCount >= 3: the chain's delta joins the history
+    int8_t clear[kMaxFlowBatch];                  // the member was (re-)armed since its last period: the history starts over first
+    int8_t force[kMaxFlowBatch];                  // -1: decide, 0: copy, 1: warp
+};
+void launch_scene_decide(const SceneDecideArgs& a, SceneState* states, int32_t* kinds, SceneRecord* records, uint32_t ring, hipStream_t stream);
+// The predicated copy behind a period's warps: a member whose kinds[m] is 0 gets each of its n_out outputs overwritten with what copy_kernel
+// writes (the valid columns of every row, levels applied); workgroups of the other members leave after one load.
+struct SceneCopyArgs {
+    int n;
+    struct Member {
+        const void* src;                          // the ring frame copyFrame shows (opticalFlowCalcSDR.cpp:173)
+        void* outs[kMaxWarpOutputs];
+        int n_out;
+        float black, white;                       // already scaled for HDR
+    } m[kMaxFlowBatch];
+};
+void launch_scene_copy(const Geom& g, const SceneCopyArgs& a, const int32_t* kinds, hipStream_t stream);
+bool dbg_bounds_read_scene(unsigned out[5], bool reset);
 // Debug-bounds records of the two kernel translation units (hf_kernels.hip / hf_flow.hip): out[0] += violations, out[1..4] = the first
 // one's site / block / thread / source line; reset: zero the records.  Return false in a build without HF_DEBUG_BOUNDS.
 bool dbg_bounds_read_kernels(unsigned out[5], bool reset);

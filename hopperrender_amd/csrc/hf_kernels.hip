@@ -14,6 +14,7 @@
 // division in apply_levels* is x * v_rcp_f32(y); "q*max + mid" is fma(q, max, mid).
 #include "hf_kernels.h"
 #include "hf_phase_plane.h"
+#include "hf_levels.h"   // ElemTraits, Levels, levels_y / levels_uv (shared with hf_scene.hip)
 #include <type_traits>
 
 #include <hip/hip_ext.h>
@@ -21,22 +22,6 @@
 namespace hf {
 
 namespace {
-
-template <typename E> struct ElemTraits;
-template <> struct ElemTraits<uint8_t> {
-    static constexpr bool hdr = false;
-    static constexpr float maxv = 255.0f;
-    static constexpr float mid = 128.0f;
-    static constexpr unsigned midu = 128u;
-    __device__ static __forceinline__ unsigned top8(uint8_t v) { return v; }
-};
-template <> struct ElemTraits<uint16_t> {
-    static constexpr bool hdr = true;
-    static constexpr float maxv = 65535.0f;
-    static constexpr float mid = 32768.0f;
-    static constexpr unsigned midu = 32768u;
-    __device__ static __forceinline__ unsigned top8(uint16_t v) { return (unsigned)(v >> 8); }  // calcDeltaSumsKernelHDR.h:98
-};
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 // 16-byte store of an output frame: nothing on the GPU reads output frames back, so they should not displace the
@@ -301,32 +286,6 @@ __global__ void pack_flow_kernel(const int16_t* __restrict__ flow, uint32_t* __r
 // ------------------------------------------------------------------------------------------
 // levels / warp / copy
 // ------------------------------------------------------------------------------------------
-struct Levels {
-    float black, white, rcp_y, rcp_uv;
-};
-__device__ __forceinline__ Levels make_levels(float black, float white) {
-    Levels l;
-    l.black = black;
-    l.white = white;
-    l.rcp_y = __builtin_amdgcn_rcpf(white - black);
-    l.rcp_uv = __builtin_amdgcn_rcpf(white);
-    return l;
-}
-template <typename E>
-__device__ __forceinline__ unsigned levels_y(float v, const Levels& l) {  // warpFrameKernelSDR.h:3-5
-    using T = ElemTraits<E>;
-    float f = ((v - l.black) * l.rcp_y) * T::maxv;
-    f = fmaxf(fminf(f, T::maxv), 0.0f);
-    return (unsigned)f & 0xFFFFu;
-}
-template <typename E>
-__device__ __forceinline__ unsigned levels_uv(float v, const Levels& l) {  // warpFrameKernelSDR.h:7-9
-    using T = ElemTraits<E>;
-    float f = __builtin_fmaf((v - T::mid) * l.rcp_uv, T::maxv, T::mid);
-    f = fmaxf(fminf(f, T::maxv), 0.0f);
-    return (unsigned)f & 0xFFFFu;
-}
-
 __device__ __forceinline__ int mirror_warp(int pos, int dim) {  // warpFrameKernelSDR.h:12-20
     int res = pos;
     if (pos >= dim - 1) res = pos - ((pos - (dim - 2)) * 2);

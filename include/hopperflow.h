@@ -268,6 +268,41 @@ int hf_batch_run_period(hf_batch* batch, const void* const* device_frames, int c
                         void* const* device_out, int mode);
 /* 1: hf_batch_run_period defers the phase planes of this batch (see above); 0: it builds them eagerly. */
 int hf_batch_defers_planes(const hf_batch* batch);
+/* ---- Whole clips through a batch: scene-cut copy periods decided on the device ----
+ * The reference's filter shows a source period as warpFrames or as copyFrame, decided from the m_totalFrameDelta history
+ * (HopperRender.cpp:959-972, 1126-1183; hf_filter_push_frame_delta / hf_filter_detect_scene_change).  The decision needs the delta of the
+ * period's own chain, so a host that takes it waits once per period (hf_wait_flow) -- which a batch cannot afford.  Here it follows the
+ * chain onto the batch stream: a tiny kernel behind the chain's last launch pushes every member's delta into the member's history (the
+ * function of csrc/hf_scene.h, the same integer arithmetic as hf_filter.cpp:130-161) and leaves its kind on the device; the period's warps
+ * are the unchanged fused launch; a predicated copy launch behind them overwrites the outputs of the members whose period turned out to be
+ * a scene change with exactly what hf_copy_frame writes (members without one leave it at once).  Nothing waits on the host.
+ *   hf_batch_scene_set        arms / re-arms one member: its history starts over (NewSegment).  source_frame_time (100-ns units, <= 0 ->
+ *                             417083) sets the 3-second window; threshold < 0 = DEFAULT_SCENE_CHANGE_THRESHOLD.  A host starts a new clip
+ *                             in a slot with hf_set_params(frame_count = 0) + hf_batch_scene_set.
+ *   hf_batch_run_period_auto  one source period of every member; only enqueues: hf_batch_update_frames_device_ref,
+ *                             hf_batch_calculate_optical_flow, the decision, hf_batch_interpolate_period, the predicated copy.  A member
+ *                             whose m_frameCount is below 3 rides the same launches (its ring always holds valid buffers) and its outputs
+ *                             are copies of the frame hf_copy_frame shows; its delta is not pushed and its flow buffers do not move, as if
+ *                             calculateOpticalFlow had not been called for it.  force_kind: NULL, or per member -1 decide, 0 copy, 1 warp.
+ *                             n_out[m] == 0 writes nothing for member m; its history still advances.  Any output mode (diagnostic modes
+ *                             warp member by member on the same stream).  Every period of an armed member must go through this call: the
+ *                             history assumes consecutive m_frameCount values (re-arm after anything else).
+ *                             HF_ERR_STATE, nothing enqueued: a batch that defers its phase planes (hf_batch_defers_planes: the period's
+ *                             warps are issued ahead of its chain there -- create the leader with HF_FLAG_BATCH_EAGER_PLANES),
+ *                             HF_FLAG_DUAL_STREAM members, a member that was never armed, a record ring that would overflow.
+ *   hf_batch_scene_read       after hf_batch_sync: the records of one member since the last read, in period order.  *n_records = how many
+ *                             there were; min(capacity, *n_records) are copied and leave the ring.  The ring holds 128 periods per member.
+ * Additive to ABI version 6: no existing struct or call changed. */
+typedef struct hf_scene_record {
+    uint32_t frame_count;        /* m_frameCount of the period */
+    uint32_t total_delta;        /* m_totalFrameDelta pushed for it (0: m_frameCount < 3, nothing pushed) */
+    int32_t kind;                /* 1 warp, 0 copy: what the period's outputs are */
+    int32_t average, d1, d2;     /* hf_filter_state: average_frame_delta, scene_change_delta1 / 2 -- of the last decision that had 3 deltas */
+} hf_scene_record;
+int hf_batch_scene_set(hf_batch* batch, int member, int64_t source_frame_time, int32_t threshold);
+int hf_batch_run_period_auto(hf_batch* batch, const void* const* device_frames, const int* n_out, const float* t, void* const* device_out,
+                             int mode, const int32_t* force_kind);
+int hf_batch_scene_read(hf_batch* batch, int member, hf_scene_record* out, int capacity, int* n_records);
 int hf_batch_sync(hf_batch* batch);   /* hf_sync() of every member */
 int hf_batch_size(const hf_batch* batch);
 const char* hf_batch_last_error(const hf_batch* batch);   /* batch == NULL: error of the last failed hf_batch_create (per thread) */
