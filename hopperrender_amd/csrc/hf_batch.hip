@@ -65,9 +65,9 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
     if (launched) *launched = false;
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     if (!n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: null argument");
-    if (mode < 0 || mode > 6) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode outside [0, 6]");
     hf_ctx* l = b->members[0];
     const int n = (int)b->members.size();
+    if (int rc = check_period_args(l, "hf_batch_interpolate_period", 0, -1, nullptr, mode)) return batch_fail(b, rc, l->err);   // the mode, ahead of all else
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     bool one_launch = !l->dual();
     for (int m = 0; m < n; m++) {
@@ -77,10 +77,8 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
         // guard and no side stream to notify here -- the one-launch path relies on that
         if (c->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_interpolate_period: a member uses asynchronous host I/O");
         one_launch = one_launch && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
-        if (n_out[m] < 0 || n_out[m] > HF_MAX_PERIOD_OUTPUTS) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: n_out outside [0, 6]");
-        for (int i = 0; i < n_out[m]; i++)
-            if (t[m * HF_MAX_PERIOD_OUTPUTS + i] > 1.0f)
-                return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");
+        if (int rc = check_period_args(c, "hf_batch_interpolate_period", n_out[m], HF_MAX_PERIOD_OUTPUTS, t + m * HF_MAX_PERIOD_OUTPUTS, mode))
+            return batch_fail(b, rc, c->err);
         one_launch = one_launch && n_out[m] >= 1;
     }
     if (one_launch) {
@@ -90,10 +88,7 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
             hf_ctx* c = b->members[m];
             fill_period(c, n_out[m], t + m * HF_MAX_PERIOD_OUTPUTS, device_out + m * HF_MAX_PERIOD_OUTPUTS, periods[m], before_chain ? 1 : 0);
             if (before_chain && c->plane_pending[1]) periods[m].plane21 = c->pp[1];
-            if (!c->warp_started && c->timing()) {   // m_warpCalcTime span of the member (opticalFlowCalcSDR.cpp:36-41), as in hf_warp_frames
-                if (hipEventRecord(c->ev_warp_start, b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipEventRecord failed");
-                c->warp_started = true;
-            }
+            if (int rc = mark_warp_start(c, b->stream)) return batch_fail(b, rc, c->err);   // as in hf_warp_frames
         }
         const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
         bool built[hf::kMaxFlowBatch];
@@ -105,7 +100,7 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
             for (int m = 0; m < n; m++) if (built[m]) b->members[m]->plane_pending[1] = false;
             return HF_OK;
         }
-        if (span >= 0) { l->ev_pool.push_back(l->spans[span].b); l->ev_pool.push_back(l->spans[span].e); l->spans.pop_back(); }
+        span_cancel(l, span);
     }
     if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
     for (int m = 0; m < n; m++)   // not eligible (diagnostic modes, odd shapes, dual-stream members): member by member
@@ -205,8 +200,7 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
         b->own_streams.push_back(m->stream);
         b->own_warp_streams.push_back(m->warp_stream);
         // one stream for the whole batch: the members' prep / warp launches and the batched chain stay in program order
-        for (auto& kv : m->graphs) hipGraphExecDestroy(kv.second);   // captured on the member's own stream
-        m->graphs.clear();
+        m->graphs.clear();   // captured on the member's own stream
         m->stream = b->stream;
         m->warp_stream = m->dual() ? b->warp_streams[(size_t)i % b->warp_streams.size()] : b->stream;
         m->batch = b;
@@ -226,10 +220,9 @@ void hf_batch_destroy(hf_batch* b) {
     for (hf_ctx* m : b->members) leave_warp_stream(m);   // the batch stream waits for every member's last warps
     if (b->stream) hipStreamSynchronize(b->stream);
     for (hipStream_t ws : b->warp_streams) hipStreamSynchronize(ws);
-    for (auto& kv : b->graphs) hipGraphExecDestroy(kv.second);
+    b->graphs.clear();
     for (size_t i = 0; i < b->members.size(); i++) {
         hf_ctx* m = b->members[i];
-        for (auto& kv : m->graphs) hipGraphExecDestroy(kv.second);
         m->graphs.clear();
         m->stream = b->own_streams[i];
         m->warp_stream = b->own_warp_streams[i];
@@ -251,56 +244,16 @@ int hf_batch_update_frames_device_ref(hf_batch* b, const void* const* device_fra
 
 namespace hfi {
 
-// hf_batch_calculate_optical_flow.  warmup_keeps_flow (hf_batch_run_period_auto): a member whose m_frameCount is below 3 rides the batched
-// launches -- its ring always holds valid buffers -- but the filter would not have calculated a flow for it (HopperRender.cpp:955), so its
-// chain writes the buffer the next real chain overwrites and nothing else of the member moves: no flow-buffer swap, no timing, no delta.
+// hf_batch_calculate_optical_flow: calculate_flow (hf_calc.hip) of the members on the batch's stream; HF_FLAG_NO_GRAPH of a member does not count.
+// Under the timeline the chain goes out launch by launch, each with the events of its own dispatch (a graph replay has no per-node timestamps).
 int batch_calculate(hf_batch* b, bool warmup_keeps_flow) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     hf_ctx* l = b->members[0];
-    const int n = (int)b->members.size();
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     if (int rc = batch_check_flow_params(b)) return rc;
-    l->tab_mode = choose_tab_mode(b->members.data(), n);
-    std::vector<int> key = {l->p.search_radius, l->p.delta_scalar, l->p.neighbor_scalar, (int)l->tab_mode};
-    for (hf_ctx* m : b->members) {
-        if (int rc = leave_warp_stream(m)) return batch_fail(b, rc, m->err);
-        key.push_back(m->ring_phase * 2 + m->blur_phase);
-    }
-    if (ensure_older_planes(b->members.data(), n, b->stream)) return batch_fail(b, HF_ERR_HIP, "phase-plane launch failed");
-    if (hf::t_launch_observer == &b->tl) {
-        // timeline: the chain's launches one by one, each with the events of its own dispatch (a graph replay has no per-node timestamps)
-        if (int rc = enqueue_flow_chain(b->members.data(), n, b->stream)) return batch_fail(b, rc, l->err);
-        for (hf_ctx* m : b->members)
-            if (!(warmup_keeps_flow && m->p.frame_count < 3))
-                if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
-        return HF_OK;
-    }
-    auto it = b->graphs.find(key);
-    if (it == b->graphs.end()) {
-        hipGraph_t graph = nullptr;
-        std::shared_lock<std::shared_mutex> capture_lock(g_capture_mutex);
-        if (hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamBeginCapture failed");
-        const int rc = enqueue_flow_chain(b->members.data(), n, b->stream);
-        const hipError_t e = hipStreamEndCapture(b->stream, &graph);
-        capture_lock.unlock();
-        if (rc || e != hipSuccess) { if (graph) hipGraphDestroy(graph); return batch_fail(b, rc ? rc : HF_ERR_HIP, rc ? l->err : "hipStreamEndCapture failed"); }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ei != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipGraphInstantiate failed");
-        if (b->graphs.size() >= 96) {
-            for (auto& kv : b->graphs) hipGraphExecDestroy(kv.second);
-            b->graphs.clear();
-        }
-        it = b->graphs.emplace(key, exec).first;
-    }
-    const int span = span_begin(l, 2);   // the leader's profile carries the batch (one span = n chains)
-    if (hipGraphLaunch(it->second, b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipGraphLaunch failed");
-    span_end(l, span);
-    if (span >= 0) l->spans[span].frames = n;
-    for (hf_ctx* m : b->members)
-        if (!(warmup_keeps_flow && m->p.frame_count < 3))
-            if (int rc = after_flow_enqueued(m, b->stream)) return batch_fail(b, rc, m->err);
+    const bool observed = hf::t_launch_observer == &b->tl;
+    if (int rc = calculate_flow(b->members.data(), (int)b->members.size(), b->stream, observed ? nullptr : &b->graphs, warmup_keeps_flow))
+        return batch_fail(b, rc == HF_ERR_OUT_OF_MEMORY ? HF_ERR_HIP : rc, l->err);   // (a batch has always reported a HIP error of its chain as HF_ERR_HIP)
     return HF_OK;
 }
 
@@ -475,7 +428,7 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
     const int n = (int)b->members.size();
     // everything that can be refused is refused before anything is enqueued
     if (!device_frames || !n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null argument");
-    if (mode < 0 || mode > 6) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode outside [0, 6]");
+    if (int rc = check_period_args(l, "hf_batch_run_period_auto", 0, -1, nullptr, mode)) return batch_fail(b, rc, l->err);
     if (b->defer_planes)
         return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: this batch defers its phase planes, so a period's warps are issued ahead of its chain and the "
                                            "decision does not exist yet; create the leader with HF_FLAG_BATCH_EAGER_PLANES");
@@ -485,10 +438,8 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
     for (int m = 0; m < n; m++) {
         if (!device_frames[m]) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null frame");
         if (b->members[m]->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: a member uses asynchronous host I/O");
-        if (n_out[m] < 0 || n_out[m] > HF_MAX_PERIOD_OUTPUTS) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: n_out outside [0, 6]");
-        for (int i = 0; i < n_out[m]; i++)
-            if (t[m * HF_MAX_PERIOD_OUTPUTS + i] > 1.0f)
-                return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");
+        if (int rc = check_period_args(b->members[m], "hf_batch_run_period_auto", n_out[m], HF_MAX_PERIOD_OUTPUTS, t + m * HF_MAX_PERIOD_OUTPUTS, mode))
+            return batch_fail(b, rc, b->members[m]->err);
         if (force_kind && (force_kind[m] < -1 || force_kind[m] > 1))
             return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: force_kind outside {-1, 0, 1}");
         if (b->scene.empty() || !b->scene[(size_t)m].armed)
@@ -518,14 +469,14 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
         da.clear[m] = sm.clear ? 1 : 0;
         da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
         hf::SceneCopyArgs::Member& cm = ca.m[m];
-        const float scale = c->g.hdr ? 256.0f : 1.0f;   // opticalFlowCalcHDR.cpp:173-174
-        cm.src = c->ring[fc >= 3 ? 0 : fc >= 2 ? 1 : 2];   // opticalFlowCalcSDR.cpp:173
+        const OutputLevels lv = output_levels(c);
+        cm.src = copy_source(c);
         cm.n_out = n_out[m];
         for (int i = 0; i < n_out[m]; i++) {
             void* o = device_out[m * HF_MAX_PERIOD_OUTPUTS + i];
             cm.outs[i] = o ? o : c->out_frame;
         }
-        cm.black = c->p.black_level * scale; cm.white = c->p.white_level * scale;
+        cm.black = lv.black; cm.white = lv.white;
     }
     hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
     if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");

@@ -9,9 +9,9 @@ using namespace hfi;
 namespace hfi {
 
 // Enqueue the refinement chains + blur (opticalFlowCalcSDR.cpp:44-116) of n contexts with identical geometry and
-// parameters as ONE set of launches on stream s (hf_kernels.h FlowBatch; n == 1: the plain call).  Capturable.
-int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
-    hf_ctx* c = cs[0];
+// parameters as ONE set of launches on stream s (hf_kernels.h FlowBatch; n == 1: the plain call).  Capturable: it only enqueues.
+int enqueue_flow_chain(const hf_ctx* const* cs, int n, hipStream_t s) {
+    const hf_ctx* c = cs[0];
     const hf::Geom& g = c->g;
     const int iters = effective_iterations(c);
     bool any_big = false;
@@ -21,9 +21,7 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
     hf::FlowBatch a{};
     a.n = n;
     for (int i = 0; i < n; i++) {
-        hf_ctx* m = cs[i];
-        m->initial_window = initial_window(g.lw, g.lh);
-        m->last_iterations = iters;
+        const hf_ctx* m = cs[i];
         hf::FlowStep& f = a.s[i];
         f.pp1 = m->pp[1];                                             // :79 frame N-1
         f.pp2 = m->pp[2];                                             // :80 frame N
@@ -61,7 +59,7 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
         const bool small = c->levels[k].window <= 32;
         for (int axis = 0; axis < (small ? 1 : 2); axis++) {
             for (int i = 0; i < n; i++) {
-                hf_ctx* m = cs[i];
+                const hf_ctx* m = cs[i];
                 hf::FlowStep& f = a.s[i];
                 f.cur = m->levels[k];
                 f.prev = k ? m->levels[k - 1] : none;             // :68-69: the chain starts from zero offsets
@@ -80,7 +78,7 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
             // sad_read follows from the previous level's window size; what makes it right is that that level wrote the tables (windows 32 .. 4
             // do, 2 does not: true while the window halves at every level and the chain ends at 2)
             if (a.s[0].sad_read && !tables_fresh)
-                return fail(c, HF_ERR_STATE, "flow chain: level %d (window %d) would read SAD tables that level %d did not write", k, c->levels[k].window, k - 1);
+                return fail(const_cast<hf_ctx*>(c), HF_ERR_STATE, "flow chain: level %d (window %d) would read SAD tables that level %d did not write", k, c->levels[k].window, k - 1);
             tables_fresh = a.s[0].sad_write != 0;
             if (small) {
                 hf::launch_flow_level_small(g, a, s);
@@ -101,9 +99,8 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
     hf::BlurBatch bb{};
     bb.n = n;
     for (int i = 0; i < n; i++) {
-        hf_ctx* m = cs[i];
-        m->last_level = iters ? m->levels[iters - 1] : none;
-        bb.s[i].last = m->last_level;
+        const hf_ctx* m = cs[i];
+        bb.s[i].last = iters ? m->levels[iters - 1] : none;
         bb.s[i].blurred = m->blurred[0];
         bb.s[i].packed = m->blurred_xy[0];
         bb.s[i].zero = any_big ? m->sums : nullptr;
@@ -111,11 +108,9 @@ int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s) {
         bb.s[i].still_out = m->still_count ? m->d_total_delta + 1 : nullptr;
     }
     hf::launch_blur_flow(g, bb, c->cfg.blur_radius, (int)(c->sums_bytes / sizeof(uint32_t)), s);  // :115-116
-    HF_HIP(c, hipGetLastError());
+    HF_HIP(const_cast<hf_ctx*>(c), hipGetLastError());
     return HF_OK;
 }
-
-int enqueue_flow_chain(hf_ctx* c) { return enqueue_flow_chain(&c, 1, c->stream); }
 
 // SAD tables or not for the NEXT chain of these contexts (one decision for a batch: its launches are shared).  The tables pay when most
 // windows keep their offsets from level to level (tests/flow_reuse_model.py: 74-96 % on the bench scene) and cost 10-15 % of the pipeline
@@ -272,9 +267,9 @@ int check_flow_params(hf_ctx* c) {
     return HF_OK;
 }
 
-// Bookkeeping behind an enqueued chain (eager, graph replay or batch): timing event, flow buffer swap.
+// Bookkeeping behind an enqueued chain (eager, graph replay or batch), the one place a chain changes its context's host state: what the
+// chain ran (hf_get_stats, hf_read_offsets), timing event, flow buffer swap.
 int after_flow_enqueued(hf_ctx* c, hipStream_t s) {
-    // a graph replay / batch leader skips enqueue_flow_chain()'s bookkeeping for this context: redo it
     const int iters = effective_iterations(c);
     c->initial_window = initial_window(c->g.lw, c->g.lh);
     c->last_iterations = iters;
@@ -307,13 +302,79 @@ int after_flow_enqueued(hf_ctx* c, hipStream_t s) {
     return HF_OK;
 }
 
+// calculateOpticalFlow of n >= 1 contexts of one geometry and one set of flow parameters as ONE chain on stream s: a context (n = 1, its own
+// stream) or the members of a batch (the batch's stream).  graphs: the cache the chain replays from, captured on a miss; nullptr: issued
+// eagerly, launch by launch.  warmup_keeps_flow (hf_batch_run_period_auto): a context whose m_frameCount is below 3 rides the launches -- its
+// ring always holds valid buffers -- but the filter would not have calculated a flow for it (HopperRender.cpp:955), so its chain writes the
+// buffer the next real chain overwrites and nothing else of it moves: no flow-buffer swap, no timing, no delta, no statistics.
+// An error is reported in cs[0]->err, whichever context it came from.
+int calculate_flow(hf_ctx* const* cs, int n, hipStream_t s, ChainGraphs* graphs, bool warmup_keeps_flow) {
+    hf_ctx* l = cs[0];
+    auto of_member = [l](const hf_ctx* m, int rc) { if (m != l) l->err = m->err; return rc; };
+    for (int i = 0; i < n; i++) if (int rc = leave_warp_stream(cs[i])) return of_member(cs[i], rc);
+    if (ensure_older_planes(cs, n, s)) return fail(l, HF_ERR_HIP, "phase-plane launch failed");
+    l->tab_mode = choose_tab_mode(cs, n);
+    hipGraphExec_t exec = nullptr;
+    if (graphs) {
+        ChainGraphs::Key key;
+        key.fill(-1);
+        key[0] = l->p.search_radius; key[1] = l->p.delta_scalar; key[2] = l->p.neighbor_scalar; key[3] = (int)l->tab_mode;
+        for (int i = 0; i < n; i++) key[4 + i] = cs[i]->ring_phase * 2 + cs[i]->blur_phase;
+        exec = graphs->find(key);
+        if (!exec) {
+            hipGraph_t graph = nullptr;
+            std::shared_lock<std::shared_mutex> capture_lock(g_capture_mutex);
+            HF_HIP(l, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            const int rc = enqueue_flow_chain(cs, n, s);
+            const hipError_t e = hipStreamEndCapture(s, &graph);
+            capture_lock.unlock();
+            if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+            HF_HIP(l, e);
+            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            hipGraphDestroy(graph);
+            HF_HIP(l, ei);
+            graphs->insert(key, exec);
+        }
+    }
+    // the leader's profile carries the chain (one span = n chains); an observed launch carries the timeline's events, not a profile span's
+    const int span = hf::t_launch_observer ? -1 : span_begin(l, 2);
+    if (exec) HF_HIP(l, hipGraphLaunch(exec, s));
+    else if (int rc = enqueue_flow_chain(cs, n, s)) return rc;
+    if (span >= 0) { span_end(l, span); l->spans[span].frames = n; }
+    for (int i = 0; i < n; i++)
+        if (!(warmup_keeps_flow && cs[i]->p.frame_count < 3))
+            if (int rc = after_flow_enqueued(cs[i], s)) return of_member(cs[i], rc);
+    return HF_OK;
+}
+
+// warpFrames' checks of its arguments (opticalFlowCalcSDR.cpp:143-146, and the output mode) for the n_out outputs of one period, for every
+// call that warps: the mode, n_out in [0, max_n_out] (max_n_out < 0: no upper bound), every blending scalar.  The error is c's.
+int check_period_args(hf_ctx* c, const char* who, int n_out, int max_n_out, const float* t, int mode) {
+    if (mode < 0 || mode > 6) return fail(c, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode %d outside [0, 6]", mode);
+    if (n_out < 0 || (max_n_out >= 0 && n_out > max_n_out)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: n_out outside [0, %d]", who, max_n_out);
+    for (int i = 0; i < n_out; i++)
+        if (t[i] > 1.0f) return fail(c, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");
+    return HF_OK;
+}
+
+// black and white level in the units of the frames' samples (opticalFlowCalcHDR.cpp:151-152,173-174)
+OutputLevels output_levels(const hf_ctx* c) { const float k = c->g.hdr ? 256.0f : 1.0f; return {c->p.black_level * k, c->p.white_level * k}; }
+
+// the frame copyFrame shows: N-2 once the ring is full, before that the oldest one there is (opticalFlowCalcSDR.cpp:173)
+void* copy_source(const hf_ctx* c) { return c->ring[c->p.frame_count >= 3 ? 0 : c->p.frame_count >= 2 ? 1 : 2]; }
+
+// m_warpCalcTime (opticalFlowCalcSDR.cpp:36-41) runs from the first warp or copy launch after a download, on the stream the caller names
+int mark_warp_start(hf_ctx* c, hipStream_t s) {
+    if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, s)); c->warp_started = true; }
+    return HF_OK;
+}
+
 // Fills the period descriptor of one context: frames N-2 / N-1, the PREVIOUS flow (:154-156), levels, outputs.
 // flow_index 1: the period is issued BEFORE the chain of its source period -- the previous flow is still the newest one
 void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index) {
-    const float scale = c->g.hdr ? 256.0f : 1.0f;
     p.frame12 = c->ring[0]; p.frame21 = c->ring[1];
     p.flow = c->blurred[flow_index]; p.flow_xy = c->blurred_xy[flow_index];
-    p.black = c->p.black_level * scale; p.white = c->p.white_level * scale;
+    p.black = output_levels(c).black; p.white = output_levels(c).white;
     p.n_out = n;
     p.counters = c->counters;
     for (int i = 0; i < n; i++) { p.ts[i] = t[i]; p.outs[i] = outs[i] ? outs[i] : c->out_frame; }
@@ -374,52 +435,17 @@ int hf_calculate_optical_flow(hf_ctx* c) {
     HF_CHECK_CTX(c);
     if (int rc = set_device(c)) return rc;
     if (int rc = check_flow_params(c)) return rc;
-    if (int rc = leave_warp_stream(c)) return rc;
-    if (ensure_older_planes(&c, 1, c->stream)) return fail(c, HF_ERR_HIP, "phase-plane launch failed");
-
-    int span = -1;
-    if (c->cfg.flags & HF_FLAG_NO_GRAPH) {
-        c->tab_mode = choose_tab_mode(&c, 1);
-        span = span_begin(c, 2);
-        if (int rc = enqueue_flow_chain(c)) return rc;
-    } else {
-        c->tab_mode = choose_tab_mode(&c, 1);
-        const auto key = std::make_tuple(c->ring_phase, c->blur_phase, c->p.search_radius, c->p.delta_scalar, c->p.neighbor_scalar, (int)c->tab_mode);
-        auto it = c->graphs.find(key);
-        if (it == c->graphs.end()) {
-            hipGraph_t graph = nullptr;
-            std::shared_lock<std::shared_mutex> capture_lock(g_capture_mutex);
-            HF_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue_flow_chain(c);
-            const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-            capture_lock.unlock();
-            if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-            HF_HIP(c, e);
-            hipGraphExec_t exec = nullptr;
-            HF_HIP(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            hipGraphDestroy(graph);
-            if (c->graphs.size() >= 96) {  // bound the cache (parameters poked by a settings UI)
-                for (auto& kv : c->graphs) hipGraphExecDestroy(kv.second);
-                c->graphs.clear();
-            }
-            it = c->graphs.emplace(key, exec).first;
-        }
-        span = span_begin(c, 2);
-        HF_HIP(c, hipGraphLaunch(it->second, c->stream));
-    }
-    span_end(c, span);
-    if (int rc = after_flow_enqueued(c, c->stream)) return rc;
+    if (int rc = calculate_flow(&c, 1, c->stream, (c->cfg.flags & HF_FLAG_NO_GRAPH) ? nullptr : &c->graphs, false)) return rc;
     if (!c->async()) return sync_ctx(c);
     return HF_OK;
 }
 
 int hf_warp_frames(hf_ctx* c, float t, int mode) {
     HF_CHECK_CTX(c);
-    if (t > 1.0f) return fail(c, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");  // :143-146
-    if (mode < 0 || mode > 6) return fail(c, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode %d outside [0, 6]", mode);
+    if (int rc = check_period_args(c, "warpFrames", 1, -1, &t, mode)) return rc;
     if (int rc = set_device(c)) return rc;
-    const float scale = c->g.hdr ? 256.0f : 1.0f;  // opticalFlowCalcHDR.cpp:151-152
-    if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, c->stream)); c->warp_started = true; }
+    const OutputLevels lv = output_levels(c);
+    if (int rc = mark_warp_start(c, c->stream)) return rc;
     if (int rc = enter_warp_stream(c)) return rc;
     if (int rc = guard_output_slot(c, c->out_target, c->warp_stream)) return rc;
     // frames N-2 / N-1 and the PREVIOUS flow (:154-156)
@@ -427,7 +453,7 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
     // execution time as rocprof reports it, not the time the launch spent queued behind other streams
     const int span = span_open(c, 0);
     hf::launch_warp(c->g, c->ring[0], c->ring[1], c->blurred[0], c->blurred_xy[0], c->out_target, t, mode,
-                    c->p.black_level * scale, c->p.white_level * scale, c->warp_stream,
+                    lv.black, lv.white, c->warp_stream,
                     span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
     if (c->on_warp_stream && !c->in_period) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
     if (int rc = note_launch(c, c->warp_stream)) return rc;
@@ -438,13 +464,12 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
 int hf_copy_frame(hf_ctx* c) {
     HF_CHECK_CTX(c);
     if (int rc = set_device(c)) return rc;
-    const float scale = c->g.hdr ? 256.0f : 1.0f;  // opticalFlowCalcHDR.cpp:173-174
-    const int idx = c->p.frame_count >= 3 ? 0 : c->p.frame_count >= 2 ? 1 : 2;  // opticalFlowCalcSDR.cpp:173
+    const OutputLevels lv = output_levels(c);
     if (int rc = leave_warp_stream(c)) return rc;
-    if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, c->stream)); c->warp_started = true; }
+    if (int rc = mark_warp_start(c, c->stream)) return rc;
     if (int rc = guard_output_slot(c, c->out_target, c->stream)) return rc;
     const int span = span_begin(c, 1);
-    hf::launch_copy(c->g, c->ring[idx], c->out_target, c->p.black_level * scale, c->p.white_level * scale, c->stream);
+    hf::launch_copy(c->g, copy_source(c), c->out_target, lv.black, lv.white, c->stream);
     span_end(c, span);
     HF_HIP(c, hipGetLastError());
     return note_launch(c, c->stream);
@@ -477,9 +502,8 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
         if (int rc = hf_calculate_optical_flow(c)) return rc;
     }
     if (int rc = set_device(c)) return rc;
-    if (mode < 0 || mode > 6) return fail(c, HF_ERR_INVALID_ARGUMENT, "warpFrames: frame output mode %d outside [0, 6]", mode);
-    for (int i = 0; i < n_out; i++)
-        if (t[i] > 1.0f) return fail(c, HF_ERR_INVALID_ARGUMENT, "Error in function warpFrames: blending scalar is greater than 1.0");
+    // (only now: the three separate calls would have updated and calculated before warpFrames refused its arguments; n_out has no upper bound here)
+    if (int rc = check_period_args(c, "hf_interpolate_period", n_out, -1, t, mode)) return rc;
     // All outputs of the period in one launch when the fast warp kernel applies: the flow is looked up once and
     // the source rows of the later outputs come from L1/L2 instead of HBM (2F + nF bytes instead of n * 3F).
     const bool fuse = n_out >= 2 && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
@@ -491,12 +515,12 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
             hf::WarpPeriod p;
             fill_period(c, n, t + done, device_out + done, p);
             for (int i = 0; i < n; i++) if (int rc = guard_output_slot(c, p.outs[i], c->warp_stream)) return rc;
-            if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, c->stream)); c->warp_started = true; }
+            if (int rc = mark_warp_start(c, c->stream)) return rc;
             const int span = span_open(c, 0);
             const bool ok = hf::launch_warp_periods(c->g, 1, &p, mode, c->warp_stream,
                                                     span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
             if (!ok) {   // shape not eligible: drop the unused span and fall back to one launch per output
-                if (span >= 0) { c->ev_pool.push_back(c->spans[span].b); c->ev_pool.push_back(c->spans[span].e); c->spans.pop_back(); }
+                span_cancel(c, span);
                 break;
             }
             if (span >= 0) c->spans[span].frames = n;

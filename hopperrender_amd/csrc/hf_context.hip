@@ -90,6 +90,10 @@ void span_end(hf_ctx* c, int idx) {
     if (idx >= 0) hipEventRecord(c->spans[idx].e, c->spans[idx].stream);
 }
 
+void span_cancel(hf_ctx* c, int idx) {   // gives back the events of the span opened last, whose launch did not happen
+    if (idx >= 0) { c->ev_pool.push_back(c->spans[idx].b); c->ev_pool.push_back(c->spans[idx].e); c->spans.pop_back(); }
+}
+
 void collect_spans(hf_ctx* c) {  // stream must be idle
     for (auto& s : c->spans) {
         float ms = 0.f;
@@ -345,7 +349,7 @@ void hf_destroy(hf_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) { leave_warp_stream(c); hipStreamSynchronize(c->stream); }  // clFinish (opticalFlowCalcSDR.cpp:186)
-    for (auto& kv : c->graphs) hipGraphExecDestroy(kv.second);
+    c->graphs.clear();
     for (int i = 0; i < 3; i++) { if (c->ring_store[i]) hipFree(c->ring_store[i]); if (c->pp[i]) hipFree(c->pp[i]); }
     if (c->tables) hipFree(c->tables);
     if (c->off_view) hipFree(c->off_view);
@@ -517,12 +521,8 @@ int hf_debug_counters_enable(hf_ctx* c, int on) {
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
     // the pointer is part of every captured launch: cached graphs of this context and of its batch are stale now
-    for (auto& kv : c->graphs) hipGraphExecDestroy(kv.second);
     c->graphs.clear();
-    if (c->batch) {
-        for (auto& kv : c->batch->graphs) hipGraphExecDestroy(kv.second);
-        c->batch->graphs.clear();
-    }
+    if (c->batch) c->batch->graphs.clear();
     if (on) {
         if (!c->counters) HF_HIP(c, hipMalloc((void**)&c->counters, hf::kCounterWords * sizeof(uint32_t)));
         HF_HIP(c, hipMemsetAsync(c->counters, 0, hf::kCounterWords * sizeof(uint32_t), c->stream));

@@ -3,7 +3,8 @@
 //   hf_context.hip   context lifetime and state: hf_create / hf_destroy (detectDevices, buffers: opticalFlowCalcSDR.cpp:206-325), parameters,
 //                    statistics, profiling spans, parity taps, device-memory helpers
 //   hf_calc.hip      the five virtuals of one context: updateFrame, calculateOpticalFlow (the refinement chain as a cached hipGraph), warpFrames,
-//                    copyFrame, downloadFrame, and the fused period calls
+//                    copyFrame, downloadFrame, and the fused period calls.  calculate_flow() there is the ONE host path of a chain, for n >= 1
+//                    contexts on a stream: hf_calculate_optical_flow is its n = 1 case, a batch's chain the same call on the batch's stream
 //   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
 //                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
 //   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async / hf_download_frame_async, hf_wait_*)
@@ -18,10 +19,11 @@
 //     2.6-8.3 MB of fills);
 //   * m_totalFrameDelta is produced on the device and copied to pinned memory inside the graph
 //     (reference: blocking 4-byte readback in the middle of the chain, opticalFlowCalcSDR.cpp:91-94);
-//   * the whole chain replays as one hipGraph keyed by (ring phase, search radius, scalars).
+//   * the whole chain replays as one hipGraph, keyed by the scalars, the table mode and every context's ring / flow-buffer phase (ChainGraphs).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -31,7 +33,6 @@
 #include <new>
 #include <shared_mutex>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/config.h"
@@ -50,6 +51,23 @@ constexpr int kMaxSteps = 32;          // 2 * log2(max window)
 
 extern std::shared_mutex g_capture_mutex;   // shared: a stream capture is in progress; exclusive: a legacy-stream copy (util_copy)
 }  // namespace hfi
+
+// The instantiated hipGraphs of the refinement chain of one context, or of one batch (hf_calc.hip calculate_flow).  What a capture bakes in,
+// and why a replay is still right:
+//   * in the key: search radius, delta and neighbour scalar (kernel arguments), the table mode (which kernels run), and per context
+//     ring_phase * 2 + blur_phase -- which of its three phase planes are frames N-1 / N and which flow buffer the chain writes;
+//   * constant for the context's life: iterations and blur radius (hf_config), HF_FLAG_NO_LAZY_ARGMIN, the levels and every device pointer but
+//     the rotating ones above (tables, window sums, SAD tables, the mapped m_totalFrameDelta slot); a batch's members never change;
+//   * clears the cache when it changes: the diagnostic counters pointer (hf_debug_counters_enable: the context's and its batch's) and the stream
+//     of the capture (hf_batch_create / hf_batch_destroy).  The key is a fixed-size array: a lookup, every period of every stream, allocates nothing.
+struct ChainGraphs {
+    static constexpr size_t kMaxEntries = 96;     // bound of the cache (parameters poked by a settings UI): a full one starts over
+    using Key = std::array<int, 4 + hf::kMaxFlowBatch>;   // R, delta scalar, neighbour scalar, table mode, then one phase per context, rest -1
+    std::map<Key, hipGraphExec_t> map;
+    hipGraphExec_t find(const Key& k) const { auto it = map.find(k); return it == map.end() ? nullptr : it->second; }
+    void insert(const Key& k, hipGraphExec_t exec) { if (map.size() >= kMaxEntries) clear(); map.emplace(k, exec); }
+    void clear() { for (auto& kv : map) hipGraphExecDestroy(kv.second); map.clear(); }
+};
 
 struct hf_ctx {
     hf::Geom g{};
@@ -141,7 +159,7 @@ struct hf_ctx {
     hipEvent_t ev_user0 = nullptr, ev_user1 = nullptr;
     bool upload_recorded = false, flow_timing_pending = false, warp_started = false;
 
-    std::map<std::tuple<int, int, int, int, int, int>, hipGraphExec_t> graphs;
+    ChainGraphs graphs;
 
     // HF_FLAG_PROFILE: event pairs around warp / copy / flow-chain launches
     struct Span { hipEvent_t b, e; int kind; hipStream_t stream; int frames = 1; };
@@ -181,8 +199,8 @@ struct hf_batch {
     std::vector<hipStream_t> own_streams;   // the members' own streams, restored by hf_batch_destroy
     std::vector<hipStream_t> own_warp_streams;
     std::vector<hipStream_t> warp_streams;  // HF_FLAG_DUAL_STREAM members: shared streams their warps are issued on
-    hipStream_t stream = nullptr;           // = members[0]'s stream, shared by all members while the batch exists
-    std::map<std::vector<int>, hipGraphExec_t> graphs;
+    hipStream_t stream = nullptr;           // the batch's own (highest-priority) stream, shared by all members while the batch exists
+    ChainGraphs graphs;
     bool defer_planes = false;              // hf_batch_run_period: grid samples at update, full plane of frame N-1 from the warp launch
     // hf_batch_run_period_auto (hf_scene.hip): allocated by the first hf_batch_scene_set
     static constexpr uint32_t kSceneRing = 128;          // records a member can hold between two hf_batch_scene_read calls
@@ -211,13 +229,14 @@ hipEvent_t pool_event(hf_ctx* c);
 int span_begin(hf_ctx* c, int kind, hipStream_t stream = nullptr);
 int span_open(hf_ctx* c, int kind);
 void span_end(hf_ctx* c, int idx);
+void span_cancel(hf_ctx* c, int idx);
 void collect_spans(hf_ctx* c);
 int sync_ctx(hf_ctx* c);
 int util_copy(int device_index, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 
 // hf_calc.hip
-int enqueue_flow_chain(hf_ctx* const* cs, int n, hipStream_t s);
-int enqueue_flow_chain(hf_ctx* c);
+int enqueue_flow_chain(const hf_ctx* const* cs, int n, hipStream_t s);
+int calculate_flow(hf_ctx* const* cs, int n, hipStream_t s, ChainGraphs* graphs, bool warmup_keeps_flow);
 bool choose_tab_mode(hf_ctx* const* cs, int n);
 int ensure_older_planes(hf_ctx* const* cs, int n, hipStream_t s);
 void finish_flow_timing(hf_ctx* c);
@@ -227,6 +246,11 @@ int rotate_after_upload(hf_ctx* c);
 int update_common(hf_ctx* c, const void* src, hipMemcpyKind kind, bool by_reference = false);
 int check_flow_params(hf_ctx* c);
 int after_flow_enqueued(hf_ctx* c, hipStream_t s);
+int check_period_args(hf_ctx* c, const char* who, int n_out, int max_n_out, const float* t, int mode);
+struct OutputLevels { float black, white; };
+OutputLevels output_levels(const hf_ctx* c);
+void* copy_source(const hf_ctx* c);
+int mark_warp_start(hf_ctx* c, hipStream_t s);
 void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index = 0);
 int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind);
 
