@@ -107,10 +107,13 @@ def run_clips(batch, clips, source_frame_time=SOURCE_24, target_frame_time=TARGE
 
     batch: a FlowBatch whose leader was created with HF_FLAG_BATCH_EAGER_PLANES (runPeriodAuto refuses a batch that defers
     its phase planes); every member starts its clip here (m_frameCount is zeroed, the history re-armed).
-    clips[i]: member i's source frames as device pointers (NV12 / P010 frames in device memory), all clips of one
-    length; a frame must stay untouched until three further periods have been issued (the ring references it).
-    Returns (outputs, kinds): outputs[i] = the clip's output frames in order as DeviceBuffer objects (the caller frees them),
-    kinds[i] = "warp" | "copy" per output frame, from the device's records."""
+    clips[i]: member i's source frames as device pointers, all clips of one length: NV12 / P010 frames in device memory, which
+    must stay untouched until three further periods have been issued (the ring references them) -- or, for a batch whose leader
+    carries HF_FLAG_BATCH_PLANAR_IN (batch.planar()[0]), planar yuv420p / yuv420p10le frames of the same size, each free as soon as
+    the batch stream has passed its period (the batch converts it into a slot of its own).
+    Returns (outputs, kinds): outputs[i] = the clip's output frames in order as DeviceBuffer objects (the caller frees them) --
+    planar ones when the leader carries HF_FLAG_BATCH_PLANAR_OUT (batch.planar()[1]), NV12 / P010 otherwise, output_frame_bytes
+    either way; kinds[i] = "warp" | "copy" per output frame, from the device's records."""
     from .calc import DeviceBuffer
     n = len(batch.members)
     if len(clips) != n or len({len(c) for c in clips}) != 1:

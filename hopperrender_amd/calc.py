@@ -335,6 +335,11 @@ class FlowBatch:
         """hf_batch_defers_planes: runPeriod samples only the grid of a new frame, the next period's warp launch builds its plane"""
         return bool(self._lib.hf_batch_defers_planes(self._b))
 
+    def planar(self):
+        """hf_batch_planar: (inputs planar, caller-owned outputs planar) -- the leader's HF_FLAG_BATCH_PLANAR_IN / HF_FLAG_BATCH_PLANAR_OUT"""
+        bits = self._lib.hf_batch_planar(self._b)
+        return bool(bits & 1), bool(bits & 2)
+
     def calculateOpticalFlow(self):
         self._check(self._lib.hf_batch_calculate_optical_flow(self._b))
 

@@ -32,14 +32,21 @@ int batch_update(hf_batch* b, const void* const* device_frames, bool defer) {
         if (int rc = leave_warp_stream(m)) return batch_fail(b, rc, m->err);
         if (m->timing() && hipEventRecord(m->ev_upload, b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipEventRecord failed");
     }
+    hf::PlanarPair pin[hf::kMaxFlowBatch];
     for (int i = 0; i < n; i++) {
         hf_ctx* m = b->members[i];
         if (m->timing()) m->upload_recorded = true;
-        m->ring[0] = const_cast<void*>(device_frames[i]);   // the ring references the caller's frame (hf_update_frame_device_ref)
+        if (b->planar_in) {   // converted into the member's own slot, as hf_update_frame_device_ref does under HF_FLAG_PLANAR_IN: no reference kept
+            m->ring[0] = m->ring_store[0];
+            pin[i] = hf::PlanarPair{device_frames[i], m->ring[0]};
+        } else {
+            m->ring[0] = const_cast<void*>(device_frames[i]);   // the ring references the caller's frame (hf_update_frame_device_ref)
+        }
         pb.frame[i] = m->ring[0];
         pb.pp[i] = m->pp[0];
         m->plane_pending[0] = defer;
     }
+    if (b->planar_in) hf::launch_planar_in_batch(l->g.hdr, l->g.H, l->g.in_stride, n, pin, b->stream);   // all new frames in one launch
     if (defer) hf::launch_prep_grid(l->g, l->pl, pb, b->stream);
     else hf::launch_prep_frames(l->g, l->pl, pb, b->stream);     // the phase planes of all new frames in one launch
     if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "phase-plane launch failed");
@@ -58,10 +65,60 @@ int batch_check_flow_params(hf_batch* b) {
     return HF_OK;
 }
 
+// HF_FLAG_BATCH_PLANAR_OUT: the semi-planar frames the period's warps (and the predicated scene copy) write instead of the caller's
+// buffers -- period_stage of every member, grown to the largest n_out seen.  Allocates, so a call runs it before its first enqueue; an
+// n_out outside [0, HF_MAX_PERIOD_OUTPUTS] is left to the check that reports it.
+int batch_ensure_out_stages(hf_batch* b, const int* n_out) {
+    if (!b->planar_out || !n_out) return HF_OK;
+    if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
+    for (size_t m = 0; m < b->members.size(); m++) {
+        hf_ctx* c = b->members[m];
+        const int want = n_out[m] <= HF_MAX_PERIOD_OUTPUTS ? n_out[m] : 0;
+        while ((int)c->period_stage.size() < want) {
+            void* p = nullptr;
+            if (hipMalloc(&p, c->out_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "cannot allocate a planar output stage");
+            }
+            c->period_stage.push_back(p);
+        }
+    }
+    return HF_OK;
+}
+
+// staged[m][i]: the stage where the caller named a buffer of its own, NULL (the member's internal output frame, which stays semi-planar) where
+// it did not.  After batch_ensure_out_stages and the checks of n_out.
+void batch_stage_targets(hf_batch* b, const int* n_out, void* const* device_out, void** staged) {
+    for (size_t m = 0; m < b->members.size(); m++)
+        for (int i = 0; i < HF_MAX_PERIOD_OUTPUTS; i++) {
+            const size_t k = m * HF_MAX_PERIOD_OUTPUTS + (size_t)i;
+            staged[k] = i < n_out[m] && device_out[k] ? b->members[m]->period_stage[(size_t)i] : nullptr;
+        }
+}
+
+// ... and behind the period's last launch: every staged output of every member into the caller's buffer, in ONE launch
+int batch_convert_outputs(hf_batch* b, const int* n_out, void* const* device_out, void* const* staged) {
+    hf::PlanarPair pairs[hf::kMaxPlanarOutPairs];
+    int np = 0;
+    for (size_t m = 0; m < b->members.size(); m++)
+        for (int i = 0; i < n_out[m]; i++) {
+            const size_t k = m * HF_MAX_PERIOD_OUTPUTS + (size_t)i;
+            if (staged[k]) pairs[np++] = hf::PlanarPair{staged[k], device_out[k]};
+        }
+    if (!np) return HF_OK;
+    const hf::Geom& g = b->members[0]->g;
+    hf::launch_planar_out_batch(g.hdr, g.H, g.out_stride, np, pairs, b->stream);
+    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "planar output launch failed");
+    return HF_OK;
+}
+
 // before_chain (hf_batch_run_period with deferred phase planes): the period's warps go out AHEAD of the period's chain -- they read
 // frames N-2 / N-1 and the previous flow, which the chain does not touch -- and build the full plane of frame N-1 that the chain
 // then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the usual order.
-int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched) {
+// convert_out (HF_FLAG_BATCH_PLANAR_OUT): the conversion of the staged outputs follows the warps here, wherever they are issued; false: the
+// caller has more to write into the stages and converts itself (hf_batch_run_period_auto).
+int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
+                      bool convert_out) {
     if (launched) *launched = false;
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     if (!n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: null argument");
@@ -81,6 +138,14 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
             return batch_fail(b, rc, c->err);
         one_launch = one_launch && n_out[m] >= 1;
     }
+    void* staged[hf::kMaxPlanarOutPairs];
+    void* const* const caller_out = device_out;
+    if (b->planar_out) {   // (the stages: allocated before anything of this call is enqueued)
+        if (int rc = batch_ensure_out_stages(b, n_out)) return rc;
+        batch_stage_targets(b, n_out, device_out, staged);
+        device_out = staged;
+    }
+    const bool convert = b->planar_out && convert_out;
     if (one_launch) {
         // every member's period in ONE launch on the batch stream (single-stream members: program order does the rest)
         hf::WarpPeriod periods[hf::kMaxFlowBatch];
@@ -98,7 +163,7 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
             if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
             if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "fused warp launch failed");
             for (int m = 0; m < n; m++) if (built[m]) b->members[m]->plane_pending[1] = false;
-            return HF_OK;
+            return convert ? batch_convert_outputs(b, n_out, caller_out, staged) : HF_OK;
         }
         span_cancel(l, span);
     }
@@ -106,7 +171,7 @@ int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const
     for (int m = 0; m < n; m++)   // not eligible (diagnostic modes, odd shapes, dual-stream members): member by member
         if (int rc = hf_interpolate_period_ex(b->members[m], nullptr, n_out[m], t + m * HF_MAX_PERIOD_OUTPUTS, device_out + m * HF_MAX_PERIOD_OUTPUTS, mode, 0))
             return batch_fail(b, rc, b->members[m]->err);
-    return HF_OK;
+    return convert ? batch_convert_outputs(b, n_out, caller_out, staged) : HF_OK;
 }
 
 namespace {
@@ -154,6 +219,14 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
         if (!m->async() || m->io_in || m->dual() != l->dual())
             return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: members must be HF_FLAG_ASYNC contexts (all single-stream or all HF_FLAG_DUAL_STREAM) without async host I/O");
     }
+    // planar frames at the batch's boundary: the leader's flags, like HF_FLAG_BATCH_EAGER_PLANES
+    const bool planar_in = (l->cfg.flags & HF_FLAG_BATCH_PLANAR_IN) != 0, planar_out = (l->cfg.flags & HF_FLAG_BATCH_PLANAR_OUT) != 0;
+    if ((planar_in && (l->g.in_stride & 1)) || (planar_out && (l->g.out_stride & 1)))
+        return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: a planar side needs an even stride (input " + std::to_string(l->g.in_stride) +
+                                                            ", output " + std::to_string(l->g.out_stride) + ")");
+    if ((planar_in || planar_out) && l->dual())
+        return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_batch_create: HF_FLAG_BATCH_PLANAR_IN / HF_FLAG_BATCH_PLANAR_OUT with HF_FLAG_DUAL_STREAM members: "
+                                                            "their warps run beside the batch stream, which the conversion launches are ordered on");
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: hipSetDevice failed");
     for (int i = 0; i < n; i++)   // before any member is touched: a failure leaves every context as it was
         if (int rc = sync_ctx(members[i])) return batch_fail(nullptr, rc, "hf_batch_create: member sync failed: " + members[i]->err);
@@ -210,6 +283,8 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     // at update time.
     b->defer_planes = !l->dual() && !(l->cfg.flags & HF_FLAG_BATCH_EAGER_PLANES) && hf::warp_period_can_build_planes(l->g, l->pl, n);
     for (int i = 0; i < n; i++) b->defer_planes = b->defer_planes && !(members[i]->cfg.flags & HF_FLAG_NO_FUSED_WARP);
+    b->planar_in = planar_in;
+    b->planar_out = planar_out;
     *out = b;
     return HF_OK;
 }
@@ -224,6 +299,10 @@ void hf_batch_destroy(hf_batch* b) {
     for (size_t i = 0; i < b->members.size(); i++) {
         hf_ctx* m = b->members[i];
         m->graphs.clear();
+        if (b->planar_out) {   // the stages of the batch's planar outputs (idle: the batch stream was synchronised above)
+            for (void* p : m->period_stage) if (p) hipFree(p);
+            m->period_stage.clear();
+        }
         m->stream = b->own_streams[i];
         m->warp_stream = b->own_warp_streams[i];
         m->on_warp_stream = false;
@@ -232,6 +311,7 @@ void hf_batch_destroy(hf_batch* b) {
     for (hipStream_t ws : b->warp_streams) hipStreamDestroy(ws);
     if (b->stream) hipStreamDestroy(b->stream);
     for (hipEvent_t e : b->tl.events) hipEventDestroy(e);
+    if (b->tl.anchor) hipEventDestroy(b->tl.anchor);
     if (b->scene_states) hipFree(b->scene_states);
     if (b->scene_kinds) hipFree(b->scene_kinds);
     if (b->scene_records) hipHostFree(b->scene_records);
@@ -272,6 +352,7 @@ int hf_batch_interpolate_period(hf_batch* b, const int* n_out, const float* t, v
 int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calculate_flow, const int* n_out, const float* t,
                         void* const* device_out, int mode) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
+    if (int rc = batch_ensure_out_stages(b, n_out)) return rc;   // (allocation: ahead of the first enqueue)
     ObserverGuard observer_guard(b);
     if (device_frames) if (int rc = batch_update(b, device_frames, b->defer_planes)) return rc;
     // Deferred phase planes: a period whose older frame still lacks its full plane issues its warps FIRST (they do not depend on
@@ -294,6 +375,8 @@ int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calcu
 }
 
 int hf_batch_defers_planes(const hf_batch* b) { return b && b->defer_planes ? 1 : 0; }
+
+int hf_batch_planar(const hf_batch* b) { return b ? (b->planar_in ? 1 : 0) | (b->planar_out ? 2 : 0) : 0; }
 
 // ---- timeline: start / stop of every dispatch of a batch on the device's clock, no profiler attached ----
 namespace {
@@ -325,6 +408,13 @@ int hf_batch_timeline_enable(hf_batch* b, int max_launches, int skip_periods) {
                 return batch_fail(b, HF_ERR_HIP, "hf_batch_timeline_enable: cannot record the reference event");
             g_tl_reference[l->device] = ref;
         }
+        // This recording's own anchor on the reference's clock.  hipEventElapsedTime is a float: minutes after the reference it resolves
+        // tens of microseconds, so a record is read against the anchor (a short, exact span) and only the anchor against the reference.
+        float anchor_ms = 0.f;
+        if ((!b->tl.anchor && hipEventCreate(&b->tl.anchor) != hipSuccess) || hipEventRecord(b->tl.anchor, b->stream) != hipSuccess ||
+            hipEventSynchronize(b->tl.anchor) != hipSuccess || hipEventElapsedTime(&anchor_ms, g_tl_reference[l->device], b->tl.anchor) != hipSuccess)
+            return batch_fail(b, HF_ERR_HIP, "hf_batch_timeline_enable: cannot record the anchor event");
+        b->tl.anchor_ms = (double)anchor_ms;
     }
     while (b->tl.events.size() < 2 * (size_t)max_launches) {
         hipEvent_t e = nullptr;
@@ -362,14 +452,14 @@ int hf_batch_timeline_read(hf_batch* b, hf_timeline_record* out, int capacity, i
         std::memset(&o, 0, sizeof(o));
         std::strncpy(o.kernel, r.name, sizeof(o.kernel) - 1);
         o.period = r.period;
-        if (hipEventElapsedTime(&t0, ref, r.b) != hipSuccess || hipEventElapsedTime(&t1, ref, r.e) != hipSuccess ||
+        if (hipEventElapsedTime(&t0, b->tl.anchor, r.b) != hipSuccess || hipEventElapsedTime(&t1, b->tl.anchor, r.e) != hipSuccess ||
             hipEventElapsedTime(&d, r.b, r.e) != hipSuccess) {
             (void)hipGetLastError();      // events of a launch that failed or never ran: flag the record, keep the others
             o.flags = 1;
             continue;
         }
-        o.start_ms = (double)t0;
-        o.end_ms = (double)t1;
+        o.start_ms = b->tl.anchor_ms + (double)t0;
+        o.end_ms = b->tl.anchor_ms + (double)t1;
         o.duration_ms = (double)d;
     }
     return HF_OK;
@@ -449,6 +539,14 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
                                                std::to_string(hf_batch::kSceneRing) + " periods); call hf_batch_sync and hf_batch_scene_read more often");
     }
     if (int rc = batch_check_flow_params(b)) return rc;
+    // HF_FLAG_BATCH_PLANAR_OUT: warps and the predicated copy write the stages; one conversion launch behind both
+    void* staged[hf::kMaxPlanarOutPairs];
+    void* const* warp_out = device_out;
+    if (b->planar_out) {
+        if (int rc = batch_ensure_out_stages(b, n_out)) return rc;
+        batch_stage_targets(b, n_out, device_out, staged);
+        warp_out = staged;
+    }
     ObserverGuard observer_guard(b);
     if (int rc = batch_update(b, device_frames, false)) return rc;
     if (int rc = batch_calculate(b, true)) return rc;
@@ -473,7 +571,7 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
         cm.src = copy_source(c);
         cm.n_out = n_out[m];
         for (int i = 0; i < n_out[m]; i++) {
-            void* o = device_out[m * HF_MAX_PERIOD_OUTPUTS + i];
+            void* o = warp_out[m * HF_MAX_PERIOD_OUTPUTS + i];
             cm.outs[i] = o ? o : c->out_frame;
         }
         cm.black = lv.black; cm.white = lv.white;
@@ -482,10 +580,10 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
     if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
     for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
     // the unchanged warps of the period (diagnostic modes and n_out == 0: member by member on the same stream), then the repair of the cut periods
-    if (int rc = hf_batch_interpolate_period(b, n_out, t, device_out, mode)) return rc;
+    if (int rc = batch_interpolate(b, n_out, t, device_out, mode, false, nullptr, false)) return rc;
     hf::launch_scene_copy(l->g, ca, b->scene_kinds, b->stream);
     if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_copy launch failed");
-    return HF_OK;
+    return b->planar_out ? batch_convert_outputs(b, n_out, device_out, staged) : HF_OK;
 }
 
 int hf_batch_scene_read(hf_batch* b, int member, hf_scene_record* out, int capacity, int* n_records) {

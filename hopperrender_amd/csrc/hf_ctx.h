@@ -144,7 +144,8 @@ struct hf_ctx {
     // planar frames at the boundary (HF_FLAG_PLANAR_IN / _OUT, hf_planar.hip); every buffer is allocated on first use
     void* in_stage[3] = {nullptr, nullptr, nullptr};             // planar host frames land here (rotates with ring_store / ev_slot_prep)
     void* out_stage[kOutRing] = {nullptr, nullptr, nullptr};     // planar frames the readbacks read ([i] paired with out_ring[i])
-    std::vector<void*> period_stage;                             // semi-planar targets of hf_interpolate_period's warps
+    std::vector<void*> period_stage;                             // semi-planar targets of hf_interpolate_period's warps; of a member of a
+                                                                 // HF_FLAG_BATCH_PLANAR_OUT batch: of the batch's period warps
     bool planar_in() const { return (cfg.flags & HF_FLAG_PLANAR_IN) != 0; }
     bool planar_out() const { return (cfg.flags & HF_FLAG_PLANAR_OUT) != 0; }
 
@@ -179,6 +180,8 @@ struct hf_timeline final : hf::LaunchObserver {
     struct Rec { const char* name; hipEvent_t b, e; int period; };
     std::vector<Rec> recs;
     std::vector<hipEvent_t> events;      // 2 per record, created when the timeline is switched on
+    hipEvent_t anchor = nullptr;         // recorded when it is switched on: the records are read against it, it against the process's reference
+    double anchor_ms = 0.0;
     size_t capacity = 0;
     int skip = 0;                        // hf_batch_run_period calls still to pass unobserved before the recording starts
     bool active = false;                 // records left: hf_batch_run_period observes its launches and issues the chain eagerly (no graph replay)
@@ -202,6 +205,9 @@ struct hf_batch {
     hipStream_t stream = nullptr;           // the batch's own (highest-priority) stream, shared by all members while the batch exists
     ChainGraphs graphs;
     bool defer_planes = false;              // hf_batch_run_period: grid samples at update, full plane of frame N-1 from the warp launch
+    // planar 4:2:0 frames at the batch's boundary (the leader's HF_FLAG_BATCH_PLANAR_IN / _OUT; hf_planar.hip): new frames are converted
+    // into the members' ring slots, caller-owned outputs out of the members' period_stage frames, by one launch each
+    bool planar_in = false, planar_out = false;
     // hf_batch_run_period_auto (hf_scene.hip): allocated by the first hf_batch_scene_set
     static constexpr uint32_t kSceneRing = 128;          // records a member can hold between two hf_batch_scene_read calls
     struct SceneMember {
@@ -259,7 +265,8 @@ int batch_fail(hf_batch* b, int code, const std::string& msg);
 int batch_update(hf_batch* b, const void* const* device_frames, bool defer);
 int batch_check_flow_params(hf_batch* b);
 int batch_calculate(hf_batch* b, bool warmup_keeps_flow);
-int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched);
+int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
+                      bool convert_out = true);
 
 // hf_async_io.hip
 int io_init(hf_ctx* c);

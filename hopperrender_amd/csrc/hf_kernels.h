@@ -182,6 +182,15 @@ void launch_copy(const Geom& g, const void* src, void* out, float black, float w
 // >> 6 out, wrapping in 16 bits).  Source and destination must not overlap.
 void launch_planar_in(int hdr, int H, int stride, const void* planar, void* semi, hipStream_t stream);
 void launch_planar_out(int hdr, int H, int stride, const void* semi, void* planar, hipStream_t stream);
+// The same for n frames of one shape in ONE launch (hf_batch; HF_FLAG_BATCH_PLANAR_IN / HF_FLAG_BATCH_PLANAR_OUT): pair i reads src and
+// writes dst.  In: planar -> semi-planar, n <= kMaxFlowBatch; out: semi-planar -> planar, n <= kMaxPlanarOutPairs.  n == 0: no launch.
+struct PlanarPair {
+    const void* src;
+    void* dst;
+};
+constexpr int kMaxPlanarOutPairs = kMaxFlowBatch * kMaxWarpOutputs;
+void launch_planar_in_batch(int hdr, int H, int stride, int n, const PlanarPair* pairs, hipStream_t stream);
+void launch_planar_out_batch(int hdr, int H, int stride, int n, const PlanarPair* pairs, hipStream_t stream);
 bool dbg_bounds_read_planar(unsigned out[5], bool reset);
 // Scene-cut copy periods of a batch, decided on the device (hf_scene.hip; hf_batch_run_period_auto).  One record per member and period:
 // the layout of hf_scene_record (include/hopperflow.h).

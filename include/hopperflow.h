@@ -95,6 +95,10 @@ typedef enum hf_output_mode {
  * first use: up to three frames per side for host I/O, one semi-planar frame per output of hf_interpolate_period. */
 #define HF_FLAG_PLANAR_IN 0x8000
 #define HF_FLAG_PLANAR_OUT 0x10000
+/* The same layout at the boundary of a BATCH.  Read only from the leader passed to hf_batch_create, like HF_FLAG_BATCH_EAGER_PLANES; a
+ * context's own calls ignore them and the members stay ordinary NV12 / P010 contexts (see hf_batch_create). */
+#define HF_FLAG_BATCH_PLANAR_IN 0x20000  /* the batch's input frames are planar */
+#define HF_FLAG_BATCH_PLANAR_OUT 0x40000 /* the batch's caller-owned outputs are planar */
 /* (0x10, 0x20, 0x100, 0x400 were round-1 stream-topology experiments -- shared warp stream, priority streams, warp
  *  turnstile, deferred phase planes -- all measured slower or equal; removed, findings in DESIGN.md section 4) */
 
@@ -268,6 +272,21 @@ int hf_batch_run_period(hf_batch* batch, const void* const* device_frames, int c
                         void* const* device_out, int mode);
 /* 1: hf_batch_run_period defers the phase planes of this batch (see above); 0: it builds them eagerly. */
 int hf_batch_defers_planes(const hf_batch* batch);
+/* ---- Planar 4:2:0 clips through a batch (layout, strides and HDR shifts: the comment at HF_FLAG_PLANAR_IN above) ----
+ * HF_FLAG_BATCH_PLANAR_IN on the leader: the device_frames of hf_batch_update_frames_device_ref, hf_batch_run_period and
+ *   hf_batch_run_period_auto are planar.  ONE launch on the batch stream, ahead of the phase-plane launch, converts the new frame of every
+ *   member into the member's own ring slot; the ring references that slot, so a caller's frame is free once the batch stream has passed the
+ *   call (no three-period hold -- the rule of hf_update_frame_device_ref under HF_FLAG_PLANAR_IN).
+ * HF_FLAG_BATCH_PLANAR_OUT on the leader: the non-NULL device_out entries of hf_batch_interpolate_period, hf_batch_run_period and
+ *   hf_batch_run_period_auto receive planar frames.  The period's warps (every output mode; in the auto call the predicated copy too)
+ *   write semi-planar frames into stages the library owns -- per member as many output frames as the largest n_out seen, allocated on
+ *   first use, freed with the batch -- and ONE launch behind them converts every output of every member into the caller's buffers.  A
+ *   NULL entry still selects the member's internal output frame, which stays NV12 / P010 (hf_download_frame_device of the member).
+ * Flow, m_totalFrameDelta, phase planes (deferred or eager), scene records and timings are those of a plain batch fed the NV12 / P010
+ * twins of the frames.  hf_batch_create returns HF_ERR_INVALID_ARGUMENT for an odd stride on a planar side and for either flag with
+ * HF_FLAG_DUAL_STREAM members; contexts with HF_FLAG_PLANAR_IN / _OUT of their own are refused as before.  Additive to ABI version 6.
+ * hf_batch_planar: bit 0 = planar in, bit 1 = planar out; 0 for NULL. */
+int hf_batch_planar(const hf_batch* batch);
 /* ---- Whole clips through a batch: scene-cut copy periods decided on the device ----
  * The reference's filter shows a source period as warpFrames or as copyFrame, decided from the m_totalFrameDelta history
  * (HopperRender.cpp:959-972, 1126-1183; hf_filter_push_frame_delta / hf_filter_detect_scene_change).  The decision needs the delta of the

@@ -34,8 +34,10 @@ typedef struct hf_timeline_record {
     char kernel[32];      /* "grid_samples", "warp_period", "plane", "large_windows_x" / "_y", "level_32" ... "level_2", "blur" */
     int32_t period;       /* hf_batch_run_period calls since the recording started */
     int32_t flags;        /* bit 0: the dispatch's events were not ready / not recorded (its launch failed): times are 0 */
-    double start_ms;      /* start / end of the dispatch, milliseconds since the process's reference event on this device (float32
-                           * resolution of a long elapsed time: ~0.25 us at 2-4 s, ~2 us at 16-32 s -- take durations from duration_ms) */
+    double start_ms;      /* start / end of the dispatch, milliseconds since the process's reference event on this device: the offset
+                           * of this recording's _enable call from the reference (one float32 elapsed time, the same for all its records:
+                           * ~2 us at 16-32 s, ~30 us after minutes -- that is how well two batches line up) plus the time since that
+                           * call (float32 of a short span: ~0.25 us at 2-4 s).  Take durations from duration_ms. */
     double end_ms;
     double duration_ms;   /* end - start of THIS dispatch, measured directly between its own two events */
 } hf_timeline_record;
