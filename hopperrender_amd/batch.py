@@ -103,7 +103,8 @@ SCENE_RECORD_RING = 128   # periods of records a batch member holds between two 
 def run_clips(batch, clips, source_frame_time=SOURCE_24, target_frame_time=TARGET_60, frame_output=2, threshold=None):
     """Whole clips through a batch, one clip per member in lockstep, with the filter's scene-change decision taken on the
     device (FlowBatch.runPeriodAuto): nothing waits per period, one sync at the end (clips longer than the record ring:
-    one more per 128 periods, to hand the records out).
+    one more per 128 periods, to hand the records out).  Any target rate up to 24 outputs per source period (24 fps -> 480 Hz is 21):
+    periods of more than 6 outputs go through hf_batch_run_period_auto_wide, in chunks of 6 outputs per member on the device.
 
     batch: a FlowBatch whose leader was created with HF_FLAG_BATCH_EAGER_PLANES (runPeriodAuto refuses a batch that defers
     its phase planes); every member starts its clip here (m_frameCount is zeroed, the history re-armed).

@@ -352,9 +352,14 @@ class FlowBatch:
         arr = (C.c_void_p * len(self.members))(*[int(p) for p in dev_ptrs])
         self._check(self._lib.hf_batch_update_frames_device_ref(self._b, arr))
 
-    def interpolatePeriod(self, scalars, out_ptrs, mode=BlendedFrame):
-        """The warps of one source period of every member in ONE launch.  scalars[i] / out_ptrs[i]: member i's lists."""
-        n, K = len(self.members), capi.HF_MAX_PERIOD_OUTPUTS
+    @staticmethod
+    def _row(scalars):
+        """Entries per member of the t / device_out arrays: HF_MAX_PERIOD_OUTPUTS (the narrow calls) unless some member's list is longer --
+        then the longest list, which the *_wide calls take (more than HF_MAX_PERIOD_OUTPUTS_WIDE: they raise the library's error)."""
+        return max([capi.HF_MAX_PERIOD_OUTPUTS] + [len(ts) for ts in scalars])
+
+    def _marshal(self, scalars, out_ptrs):
+        n, K = len(self.members), self._row(scalars)
         counts = (C.c_int * n)(*[len(ts) for ts in scalars])
         t = (C.c_float * (n * K))()
         outs = (C.c_void_p * (n * K))()
@@ -362,27 +367,33 @@ class FlowBatch:
             for k, x in enumerate(ts):
                 t[i * K + k] = float(x)
                 outs[i * K + k] = int(out_ptrs[i][k])
-        self._check(self._lib.hf_batch_interpolate_period(self._b, counts, t, outs, int(mode)))
+        return K, counts, t, outs
+
+    def interpolatePeriod(self, scalars, out_ptrs, mode=BlendedFrame):
+        """The warps of one source period of every member in ONE launch per chunk of 6 outputs.  scalars[i] / out_ptrs[i]: member i's lists
+        (more than 6 entries in some list: hf_batch_interpolate_period_wide)."""
+        K, counts, t, outs = self._marshal(scalars, out_ptrs)
+        if K > capi.HF_MAX_PERIOD_OUTPUTS:
+            self._check(self._lib.hf_batch_interpolate_period_wide(self._b, K, counts, t, outs, int(mode)))
+        else:
+            self._check(self._lib.hf_batch_interpolate_period(self._b, counts, t, outs, int(mode)))
 
     def preparePeriod(self, dev_ptrs, scalars, out_ptrs, mode=BlendedFrame, calculate_flow=True):
         """The arguments of one hf_batch_run_period call, marshalled once (a driver's schedule is known ahead of time);
-        dev_ptrs / scalars may be None to skip the update / the warps."""
-        n, K = len(self.members), capi.HF_MAX_PERIOD_OUTPUTS
+        dev_ptrs / scalars may be None to skip the update / the warps.  A list of more than 6 scalars makes it the argument tuple of
+        hf_batch_run_period_wide (one element more: the row, after calculate_flow); runPeriod tells the two apart by their length."""
+        n = len(self.members)
         frames = (C.c_void_p * n)(*[int(p) for p in dev_ptrs]) if dev_ptrs is not None else None
-        counts = t = outs = None
+        K, counts, t, outs = capi.HF_MAX_PERIOD_OUTPUTS, None, None, None
         if scalars is not None:
-            counts = (C.c_int * n)(*[len(ts) for ts in scalars])
-            t = (C.c_float * (n * K))()
-            outs = (C.c_void_p * (n * K))()
-            for i, ts in enumerate(scalars):
-                for k, x in enumerate(ts):
-                    t[i * K + k] = float(x)
-                    outs[i * K + k] = int(out_ptrs[i][k])
+            K, counts, t, outs = self._marshal(scalars, out_ptrs)
+        if K > capi.HF_MAX_PERIOD_OUTPUTS:
+            return (frames, 1 if calculate_flow else 0, K, counts, t, outs, int(mode))
         return (frames, 1 if calculate_flow else 0, counts, t, outs, int(mode))
 
     def runPeriod(self, prepared):
         """updateFramesDeviceRef + calculateOpticalFlow + interpolatePeriod of one source period in ONE native call."""
-        rc = self._lib.hf_batch_run_period(self._b, *prepared)
+        rc = (self._lib.hf_batch_run_period if len(prepared) == 6 else self._lib.hf_batch_run_period_wide)(self._b, *prepared)
         if rc != 0:
             self._check(rc)
 
@@ -392,10 +403,16 @@ class FlowBatch:
 
     def runPeriodAuto(self, dev_ptrs, scalars, out_ptrs, mode=BlendedFrame, force_kind=None):
         """hf_batch_run_period_auto: one source period of every member, warp or copy decided on the device; only enqueues.
-        scalars[i] / out_ptrs[i]: member i's lists (an empty list: no output); force_kind: None or per member -1 decide / 0 copy / 1 warp."""
-        frames, _, counts, t, outs, mode = self.preparePeriod(dev_ptrs, scalars, out_ptrs, mode)
+        scalars[i] / out_ptrs[i]: member i's lists (an empty list: no output; more than 6 entries in some list:
+        hf_batch_run_period_auto_wide); force_kind: None or per member -1 decide / 0 copy / 1 warp."""
+        prepared = self.preparePeriod(dev_ptrs, scalars, out_ptrs, mode)
         force = (C.c_int32 * len(self.members))(*[int(k) for k in force_kind]) if force_kind is not None else None
-        rc = self._lib.hf_batch_run_period_auto(self._b, frames, counts, t, outs, mode, force)
+        if len(prepared) == 6:
+            frames, _, counts, t, outs, mode = prepared
+            rc = self._lib.hf_batch_run_period_auto(self._b, frames, counts, t, outs, mode, force)
+        else:
+            frames, _, row, counts, t, outs, mode = prepared
+            rc = self._lib.hf_batch_run_period_auto_wide(self._b, frames, row, counts, t, outs, mode, force)
         if rc != 0:
             self._check(rc)
 

@@ -24,6 +24,7 @@ HF_FLAG_PLANAR_OUT = 0x10000    # frames handed back are planar 4:2:0
 HF_FLAG_BATCH_PLANAR_IN = 0x20000    # on a batch's leader: the batch's input frames are planar 4:2:0
 HF_FLAG_BATCH_PLANAR_OUT = 0x40000   # on a batch's leader: the batch's caller-owned outputs are planar 4:2:0
 HF_MAX_PERIOD_OUTPUTS = 6
+HF_MAX_PERIOD_OUTPUTS_WIDE = 24   # the *_wide period calls: 23.976 fps -> 480 Hz is 21 outputs per source period
 
 (HF_OK, HF_ERR_INVALID_ARGUMENT, HF_ERR_NO_DEVICE, HF_ERR_OUT_OF_MEMORY, HF_ERR_HIP, HF_ERR_STATE) = (0, -1, -2, -3, -4, -5)
 
@@ -143,6 +144,9 @@ SIGNATURES = {
     "hf_batch_scene_set": (_i, [_vp, _i, C.c_int64, C.c_int32]),
     "hf_batch_run_period_auto": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i, C.POINTER(C.c_int32)]),
     "hf_batch_scene_read": (_i, [_vp, _i, C.POINTER(HfSceneRecord), _i, C.POINTER(_i)]),
+    "hf_batch_interpolate_period_wide": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i]),
+    "hf_batch_run_period_wide": (_i, [_vp, C.POINTER(_vp), _i, _i, C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i]),
+    "hf_batch_run_period_auto_wide": (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(C.c_float), C.POINTER(_vp), _i, C.POINTER(C.c_int32)]),
     "hf_batch_sync": (_i, [_vp]),
     "hf_batch_size": (_i, [_vp]),
     "hf_batch_timeline_enable": (_i, [_vp, _i, _i]),

@@ -66,14 +66,15 @@ int batch_check_flow_params(hf_batch* b) {
 }
 
 // HF_FLAG_BATCH_PLANAR_OUT: the semi-planar frames the period's warps (and the predicated scene copy) write instead of the caller's
-// buffers -- period_stage of every member, grown to the largest n_out seen.  Allocates, so a call runs it before its first enqueue; an
-// n_out outside [0, HF_MAX_PERIOD_OUTPUTS] is left to the check that reports it.
-int batch_ensure_out_stages(hf_batch* b, const int* n_out) {
+// buffers -- period_stage of every member, grown to the largest n_out seen, kMaxWarpOutputs at the most: a wider period goes out in chunks
+// of that many outputs, each converted before the next one's warps reuse the stages (stream order).  Allocates, so a call runs it before
+// its first enqueue; an n_out outside [0, row] is left to the check that reports it.
+int batch_ensure_out_stages(hf_batch* b, int row, const int* n_out) {
     if (!b->planar_out || !n_out) return HF_OK;
     if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     for (size_t m = 0; m < b->members.size(); m++) {
         hf_ctx* c = b->members[m];
-        const int want = n_out[m] <= HF_MAX_PERIOD_OUTPUTS ? n_out[m] : 0;
+        const int want = n_out[m] > row ? 0 : n_out[m] < hf::kMaxWarpOutputs ? n_out[m] : hf::kMaxWarpOutputs;
         while ((int)c->period_stage.size() < want) {
             void* p = nullptr;
             if (hipMalloc(&p, c->out_bytes) != hipSuccess) {
@@ -86,24 +87,26 @@ int batch_ensure_out_stages(hf_batch* b, const int* n_out) {
     return HF_OK;
 }
 
-// staged[m][i]: the stage where the caller named a buffer of its own, NULL (the member's internal output frame, which stays semi-planar) where
-// it did not.  After batch_ensure_out_stages and the checks of n_out.
-void batch_stage_targets(hf_batch* b, const int* n_out, void* const* device_out, void** staged) {
+// The targets of one chunk of a period (hf_launch_plan.h plan_period_chunks): outs[m][i] is where output `first + i` of member m is written,
+// for i < count[m].  Plain batch: the caller's entry (NULL: the member's internal output frame).  HF_FLAG_BATCH_PLANAR_OUT: the member's
+// stage i where the caller named a buffer of its own, NULL (the internal frame, which stays semi-planar) where it did not.  After
+// batch_ensure_out_stages and the checks of n_out.
+void batch_chunk_targets(hf_batch* b, int row, int first, const uint8_t* count, void* const* device_out, void** outs) {
     for (size_t m = 0; m < b->members.size(); m++)
-        for (int i = 0; i < HF_MAX_PERIOD_OUTPUTS; i++) {
-            const size_t k = m * HF_MAX_PERIOD_OUTPUTS + (size_t)i;
-            staged[k] = i < n_out[m] && device_out[k] ? b->members[m]->period_stage[(size_t)i] : nullptr;
+        for (int i = 0; i < count[m]; i++) {
+            void* o = device_out[m * (size_t)row + (size_t)(first + i)];
+            outs[m * hf::kMaxWarpOutputs + (size_t)i] = o && b->planar_out ? b->members[m]->period_stage[(size_t)i] : o;
         }
 }
 
-// ... and behind the period's last launch: every staged output of every member into the caller's buffer, in ONE launch
-int batch_convert_outputs(hf_batch* b, const int* n_out, void* const* device_out, void* const* staged) {
+// ... and behind the chunk's last launch: every staged output of every member into the caller's buffer, in ONE launch
+int batch_convert_chunk(hf_batch* b, int row, int first, const uint8_t* count, void* const* device_out, void* const* outs) {
     hf::PlanarPair pairs[hf::kMaxPlanarOutPairs];
     int np = 0;
     for (size_t m = 0; m < b->members.size(); m++)
-        for (int i = 0; i < n_out[m]; i++) {
-            const size_t k = m * HF_MAX_PERIOD_OUTPUTS + (size_t)i;
-            if (staged[k]) pairs[np++] = hf::PlanarPair{staged[k], device_out[k]};
+        for (int i = 0; i < count[m]; i++) {
+            void* o = device_out[m * (size_t)row + (size_t)(first + i)];
+            if (o) pairs[np++] = hf::PlanarPair{outs[m * hf::kMaxWarpOutputs + (size_t)i], o};
         }
     if (!np) return HF_OK;
     const hf::Geom& g = b->members[0]->g;
@@ -112,75 +115,116 @@ int batch_convert_outputs(hf_batch* b, const int* n_out, void* const* device_out
     return HF_OK;
 }
 
-// before_chain (hf_batch_run_period with deferred phase planes): the period's warps go out AHEAD of the period's chain -- they read
-// frames N-2 / N-1 and the previous flow, which the chain does not touch -- and build the full plane of frame N-1 that the chain
-// then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the usual order.
-// convert_out (HF_FLAG_BATCH_PLANAR_OUT): the conversion of the staged outputs follows the warps here, wherever they are issued; false: the
-// caller has more to write into the stages and converts itself (hf_batch_run_period_auto).
-int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
-                      bool convert_out) {
+// The warps of one source period of every member, chunk by chunk (hf_launch_plan.h plan_period_chunks; a period of up to kMaxWarpOutputs
+// outputs per member is one chunk).  t and device_out are [batch size][row] arrays.  Per chunk: ONE fused launch over the members that have
+// outputs in it -- they keep their batch index wherever the device looks one up (scene_kinds, SceneCopyArgs) -- or, where that does not
+// qualify (diagnostic modes, odd shapes, a misaligned output, dual-stream members), those members one by one; behind it the predicated
+// copy of the chunk (copy != nullptr: hf_batch_run_period_auto; src and levels per member are the caller's, outputs and counts are filled
+// in here) and, under HF_FLAG_BATCH_PLANAR_OUT, the conversion of the chunk's staged outputs.  Stream order lets every chunk reuse the
+// same stages.  Chunks [first_chunk, ...) are issued.
+// before_chain (hf_batch_run_period with deferred phase planes): chunk 0 -- every member has outputs in it -- goes out AHEAD of the
+// period's chain: it reads frames N-2 / N-1 and the previous flow, which the chain does not touch, and builds the full plane of frame N-1
+// that the chain then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the
+// usual order.  The later chunks of the period always follow the chain (first_chunk = 1): the member-by-member path reads flow buffer 0,
+// which is the previous flow only once the chain has swapped the buffers.
+int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
+                      hf::SceneCopyArgs* copy, int first_chunk) {
     if (launched) *launched = false;
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     if (!n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: null argument");
     hf_ctx* l = b->members[0];
     const int n = (int)b->members.size();
     if (int rc = check_period_args(l, "hf_batch_interpolate_period", 0, -1, nullptr, mode)) return batch_fail(b, rc, l->err);   // the mode, ahead of all else
+    if (row < 1 || row > HF_MAX_PERIOD_OUTPUTS_WIDE)
+        return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: row outside [1, " + std::to_string(HF_MAX_PERIOD_OUTPUTS_WIDE) + "]");
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    bool one_launch = !l->dual();
+    bool fused = !l->dual(), all_have = true;
     for (int m = 0; m < n; m++) {
         hf_ctx* c = b->members[m];
         if (!c) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "null context");
         // batch members have no asynchronous host I/O (hf_batch_create / hf_*_async enforce it), so there is no output-ring slot to
         // guard and no side stream to notify here -- the one-launch path relies on that
         if (c->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_interpolate_period: a member uses asynchronous host I/O");
-        one_launch = one_launch && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
-        if (int rc = check_period_args(c, "hf_batch_interpolate_period", n_out[m], HF_MAX_PERIOD_OUTPUTS, t + m * HF_MAX_PERIOD_OUTPUTS, mode))
-            return batch_fail(b, rc, c->err);
-        one_launch = one_launch && n_out[m] >= 1;
+        fused = fused && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
+        if (int rc = check_period_args(c, "hf_batch_interpolate_period", n_out[m], row, t + (size_t)m * row, mode)) return batch_fail(b, rc, c->err);
+        all_have = all_have && n_out[m] >= 1;
     }
-    void* staged[hf::kMaxPlanarOutPairs];
-    void* const* const caller_out = device_out;
-    if (b->planar_out) {   // (the stages: allocated before anything of this call is enqueued)
-        if (int rc = batch_ensure_out_stages(b, n_out)) return rc;
-        batch_stage_targets(b, n_out, device_out, staged);
-        device_out = staged;
-    }
-    const bool convert = b->planar_out && convert_out;
-    if (one_launch) {
-        // every member's period in ONE launch on the batch stream (single-stream members: program order does the rest)
+    if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;   // (the stages: allocated before anything of this call is enqueued)
+    const hf::PeriodChunks pc = hf::plan_period_chunks(n, n_out);
+    static_assert(hf::kMaxPeriodOutputsWide == HF_MAX_PERIOD_OUTPUTS_WIDE && hf::kMaxWarpOutputs == HF_MAX_PERIOD_OUTPUTS, "the header's limits are the plan's");
+    if (before_chain && !(fused && all_have)) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
+    // (the auto call issues its predicated copy in a period without any output too: its launches do not depend on the schedule)
+    const int end = before_chain ? 1 : pc.n_chunks ? pc.n_chunks : copy ? 1 : 0;
+    for (int ch = first_chunk; ch < end; ch++) {
+        const uint8_t* count = pc.count[ch];
+        const int first = ch * hf::kMaxWarpOutputs;
+        void* outs[hf::kMaxPlanarOutPairs];
+        batch_chunk_targets(b, row, first, count, device_out, outs);
         hf::WarpPeriod periods[hf::kMaxFlowBatch];
-        for (int m = 0; m < n; m++) {
-            hf_ctx* c = b->members[m];
-            fill_period(c, n_out[m], t + m * HF_MAX_PERIOD_OUTPUTS, device_out + m * HF_MAX_PERIOD_OUTPUTS, periods[m], before_chain ? 1 : 0);
-            if (before_chain && c->plane_pending[1]) periods[m].plane21 = c->pp[1];
-            if (int rc = mark_warp_start(c, b->stream)) return batch_fail(b, rc, c->err);   // as in hf_warp_frames
+        int who[hf::kMaxFlowBatch], np = 0, frames = 0;
+        for (int m = 0; m < n; m++) if (count[m]) { who[np++] = m; frames += count[m]; }
+        bool done = np == 0;
+        if (fused && np) {
+            // the chunk of every member in ONE launch on the batch stream (single-stream members: program order does the rest)
+            for (int k = 0; k < np; k++) {
+                const int m = who[k];
+                hf_ctx* c = b->members[m];
+                fill_period(c, count[m], t + (size_t)m * row + first, outs + (size_t)m * hf::kMaxWarpOutputs, periods[k], before_chain ? 1 : 0);
+                if (before_chain && c->plane_pending[1]) periods[k].plane21 = c->pp[1];
+                if (int rc = mark_warp_start(c, b->stream)) return batch_fail(b, rc, c->err);   // as in hf_warp_frames
+            }
+            const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
+            bool built[hf::kMaxFlowBatch];
+            if (hf::launch_warp_periods(l->g, np, periods, mode, b->stream, span >= 0 ? l->spans[span].b : nullptr, span >= 0 ? l->spans[span].e : nullptr,
+                                        before_chain ? &l->pl : nullptr, built)) {
+                if (span >= 0) l->spans[span].frames = frames;
+                if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
+                if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "fused warp launch failed");
+                for (int k = 0; k < np; k++) if (built[k]) b->members[who[k]]->plane_pending[1] = false;
+                done = true;
+            } else {
+                span_cancel(l, span);
+            }
         }
-        const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
-        bool built[hf::kMaxFlowBatch];
-        if (hf::launch_warp_periods(l->g, n, periods, mode, b->stream, span >= 0 ? l->spans[span].b : nullptr, span >= 0 ? l->spans[span].e : nullptr,
-                                    before_chain ? &l->pl : nullptr, built)) {
-            if (span >= 0) { int f = 0; for (int m = 0; m < n; m++) f += n_out[m]; l->spans[span].frames = f; }
-            if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
-            if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "fused warp launch failed");
-            for (int m = 0; m < n; m++) if (built[m]) b->members[m]->plane_pending[1] = false;
-            return convert ? batch_convert_outputs(b, n_out, caller_out, staged) : HF_OK;
+        if (!done) {
+            if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
+            for (int k = 0; k < np; k++) {    // not eligible (diagnostic modes, odd shapes, dual-stream members): member by member
+                const int m = who[k];
+                if (int rc = hf_interpolate_period_ex(b->members[m], nullptr, count[m], t + (size_t)m * row + first, outs + (size_t)m * hf::kMaxWarpOutputs, mode, 0))
+                    return batch_fail(b, rc, b->members[m]->err);
+            }
         }
-        span_cancel(l, span);
+        if (copy) {   // the repair of the cut periods: this chunk's outputs of the members whose kind is copy
+            for (int m = 0; m < n; m++) {
+                hf::SceneCopyArgs::Member& cm = copy->m[m];
+                cm.n_out = count[m];
+                for (int i = 0; i < count[m]; i++) {
+                    void* o = outs[(size_t)m * hf::kMaxWarpOutputs + (size_t)i];
+                    cm.outs[i] = o ? o : b->members[m]->out_frame;
+                }
+            }
+            hf::launch_scene_copy(l->g, *copy, b->scene_kinds, b->stream);
+            if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_copy launch failed");
+        }
+        if (b->planar_out) if (int rc = batch_convert_chunk(b, row, first, count, device_out, outs)) return rc;
     }
-    if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
-    for (int m = 0; m < n; m++)   // not eligible (diagnostic modes, odd shapes, dual-stream members): member by member
-        if (int rc = hf_interpolate_period_ex(b->members[m], nullptr, n_out[m], t + m * HF_MAX_PERIOD_OUTPUTS, device_out + m * HF_MAX_PERIOD_OUTPUTS, mode, 0))
-            return batch_fail(b, rc, b->members[m]->err);
-    return convert ? batch_convert_outputs(b, n_out, caller_out, staged) : HF_OK;
+    return HF_OK;
 }
+
+// the launches a period of `chunks` chunks adds to a one-chunk period's: per further chunk up to two fused warp launches (17 members and
+// more), the predicated copy and the planar conversion
+int timeline_reserve(int chunks) { return 32 + (chunks > 1 ? 4 * (chunks - 1) : 0); }
 
 namespace {
 // timeline on: every launch of a period call carries its own start / stop events (hf_kernels.h HF_LAUNCH)
 struct ObserverGuard {
     hf_batch* b;
-    explicit ObserverGuard(hf_batch* x) : b(nullptr) {
+    // chunks: of the period about to be issued (plan_period_chunks).  The end of the last period left room for a one-chunk period; a wider one
+    // needs timeline_reserve(chunks) free records, or the recording ends here
+    explicit ObserverGuard(hf_batch* x, int chunks = 1) : b(nullptr) {
         if (!x->tl.active) return;
         if (x->tl.skip > 0) { x->tl.skip--; return; }      // armed, not recording yet
+        if (chunks > 1 && x->tl.recs.size() + (size_t)timeline_reserve(chunks) > x->tl.capacity) { x->tl.active = false; return; }
         b = x;
         hf::t_launch_observer = &b->tl;
     }
@@ -345,18 +389,23 @@ int hf_batch_calculate_optical_flow(hf_batch* b) { return batch_calculate(b, fal
 
 int hf_batch_size(const hf_batch* b) { return b ? (int)b->members.size() : 0; }
 
-int hf_batch_interpolate_period(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode) {
-    return batch_interpolate(b, n_out, t, device_out, mode, false, nullptr);
-}
+}  // extern "C"
 
-int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calculate_flow, const int* n_out, const float* t,
-                        void* const* device_out, int mode) {
+namespace hfi {
+
+// hf_batch_run_period / hf_batch_run_period_wide: t and device_out are [batch size][row] arrays
+int batch_run_period(hf_batch* b, const void* const* device_frames, int calculate_flow, int row, const int* n_out, const float* t,
+                     void* const* device_out, int mode) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
-    if (int rc = batch_ensure_out_stages(b, n_out)) return rc;   // (allocation: ahead of the first enqueue)
-    ObserverGuard observer_guard(b);
+    if (row < 1 || row > HF_MAX_PERIOD_OUTPUTS_WIDE)   // (not an argument of the three separate calls' update or chain: refused before either)
+        return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period: row outside [1, " + std::to_string(HF_MAX_PERIOD_OUTPUTS_WIDE) + "]");
+    if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;   // (allocation: ahead of the first enqueue)
+    const int chunks = n_out ? hf::plan_period_chunks((int)b->members.size(), n_out).n_chunks : 0;
+    ObserverGuard observer_guard(b, chunks);
     if (device_frames) if (int rc = batch_update(b, device_frames, b->defer_planes)) return rc;
     // Deferred phase planes: a period whose older frame still lacks its full plane issues its warps FIRST (they do not depend on
-    // this period's chain) and lets that launch build the plane; same results as the order of the three calls.
+    // this period's chain) and lets that launch build the plane; same results as the order of the three calls.  Of a period of several
+    // chunks only chunk 0, which holds every member, goes first.
     bool warped = false;
     if (n_out && calculate_flow && b->defer_planes && mode >= 0 && mode <= 2) {
         // The early warps must not write the caller's output buffers in a period whose flow calculation is going to be refused: the three
@@ -367,11 +416,33 @@ int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calcu
         // (an argument error of this early attempt -- nothing enqueued, `warped` false -- is not reported here: the period then takes the usual
         //  order below, which reports the same error where the three separate calls would, after the update and the chain; a launch that was
         //  enqueued and failed is reported at once)
-        if (pending) if (int rc = batch_interpolate(b, n_out, t, device_out, mode, true, &warped)) { if (warped) return rc; }
+        if (pending) if (int rc = batch_interpolate(b, row, n_out, t, device_out, mode, true, &warped)) { if (warped) return rc; }
     }
     if (calculate_flow) if (int rc = hf_batch_calculate_optical_flow(b)) return rc;
-    if (n_out && !warped) if (int rc = hf_batch_interpolate_period(b, n_out, t, device_out, mode)) return rc;
+    if (n_out && (!warped || chunks > 1)) if (int rc = batch_interpolate(b, row, n_out, t, device_out, mode, false, nullptr, nullptr, warped ? 1 : 0)) return rc;
     return HF_OK;
+}
+
+}  // namespace hfi
+
+extern "C" {
+
+int hf_batch_interpolate_period(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode) {
+    return batch_interpolate(b, HF_MAX_PERIOD_OUTPUTS, n_out, t, device_out, mode, false, nullptr);
+}
+
+int hf_batch_interpolate_period_wide(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode) {
+    return batch_interpolate(b, row, n_out, t, device_out, mode, false, nullptr);
+}
+
+int hf_batch_run_period(hf_batch* b, const void* const* device_frames, int calculate_flow, const int* n_out, const float* t,
+                        void* const* device_out, int mode) {
+    return batch_run_period(b, device_frames, calculate_flow, HF_MAX_PERIOD_OUTPUTS, n_out, t, device_out, mode);
+}
+
+int hf_batch_run_period_wide(hf_batch* b, const void* const* device_frames, int calculate_flow, int row, const int* n_out, const float* t,
+                             void* const* device_out, int mode) {
+    return batch_run_period(b, device_frames, calculate_flow, row, n_out, t, device_out, mode);
 }
 
 int hf_batch_defers_planes(const hf_batch* b) { return b && b->defer_planes ? 1 : 0; }
@@ -511,14 +582,21 @@ int hf_batch_scene_set(hf_batch* b, int member, int64_t source_frame_time, int32
     return HF_OK;
 }
 
-int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, const int* n_out, const float* t, void* const* device_out,
-                             int mode, const int32_t* force_kind) {
+}  // extern "C"
+
+namespace hfi {
+
+// hf_batch_run_period_auto / hf_batch_run_period_auto_wide: t and device_out are [batch size][row] arrays
+int batch_run_period_auto(hf_batch* b, const void* const* device_frames, int row, const int* n_out, const float* t, void* const* device_out,
+                          int mode, const int32_t* force_kind) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     hf_ctx* l = b->members[0];
     const int n = (int)b->members.size();
     // everything that can be refused is refused before anything is enqueued
     if (!device_frames || !n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null argument");
     if (int rc = check_period_args(l, "hf_batch_run_period_auto", 0, -1, nullptr, mode)) return batch_fail(b, rc, l->err);
+    if (row < 1 || row > HF_MAX_PERIOD_OUTPUTS_WIDE)
+        return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: row outside [1, " + std::to_string(HF_MAX_PERIOD_OUTPUTS_WIDE) + "]");
     if (b->defer_planes)
         return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: this batch defers its phase planes, so a period's warps are issued ahead of its chain and the "
                                            "decision does not exist yet; create the leader with HF_FLAG_BATCH_EAGER_PLANES");
@@ -528,7 +606,7 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
     for (int m = 0; m < n; m++) {
         if (!device_frames[m]) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: null frame");
         if (b->members[m]->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: a member uses asynchronous host I/O");
-        if (int rc = check_period_args(b->members[m], "hf_batch_run_period_auto", n_out[m], HF_MAX_PERIOD_OUTPUTS, t + m * HF_MAX_PERIOD_OUTPUTS, mode))
+        if (int rc = check_period_args(b->members[m], "hf_batch_run_period_auto", n_out[m], row, t + (size_t)m * row, mode))
             return batch_fail(b, rc, b->members[m]->err);
         if (force_kind && (force_kind[m] < -1 || force_kind[m] > 1))
             return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: force_kind outside {-1, 0, 1}");
@@ -539,15 +617,9 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
                                                std::to_string(hf_batch::kSceneRing) + " periods); call hf_batch_sync and hf_batch_scene_read more often");
     }
     if (int rc = batch_check_flow_params(b)) return rc;
-    // HF_FLAG_BATCH_PLANAR_OUT: warps and the predicated copy write the stages; one conversion launch behind both
-    void* staged[hf::kMaxPlanarOutPairs];
-    void* const* warp_out = device_out;
-    if (b->planar_out) {
-        if (int rc = batch_ensure_out_stages(b, n_out)) return rc;
-        batch_stage_targets(b, n_out, device_out, staged);
-        warp_out = staged;
-    }
-    ObserverGuard observer_guard(b);
+    // HF_FLAG_BATCH_PLANAR_OUT: warps and the predicated copy write the stages; one conversion launch behind both, per chunk
+    if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;
+    ObserverGuard observer_guard(b, hf::plan_period_chunks(n, n_out).n_chunks);
     if (int rc = batch_update(b, device_frames, false)) return rc;
     if (int rc = batch_calculate(b, true)) return rc;
     // the decision, behind the chain's last launch
@@ -568,22 +640,28 @@ int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, cons
         da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
         hf::SceneCopyArgs::Member& cm = ca.m[m];
         const OutputLevels lv = output_levels(c);
-        cm.src = copy_source(c);
-        cm.n_out = n_out[m];
-        for (int i = 0; i < n_out[m]; i++) {
-            void* o = warp_out[m * HF_MAX_PERIOD_OUTPUTS + i];
-            cm.outs[i] = o ? o : c->out_frame;
-        }
+        cm.src = copy_source(c);          // (outputs and their number: per chunk, batch_interpolate)
         cm.black = lv.black; cm.white = lv.white;
     }
     hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
     if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
     for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
-    // the unchanged warps of the period (diagnostic modes and n_out == 0: member by member on the same stream), then the repair of the cut periods
-    if (int rc = batch_interpolate(b, n_out, t, device_out, mode, false, nullptr, false)) return rc;
-    hf::launch_scene_copy(l->g, ca, b->scene_kinds, b->stream);
-    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_copy launch failed");
-    return b->planar_out ? batch_convert_outputs(b, n_out, device_out, staged) : HF_OK;
+    // the unchanged warps of the period (diagnostic modes: member by member on the same stream) and the repair of the cut periods, chunk by chunk
+    return batch_interpolate(b, row, n_out, t, device_out, mode, false, nullptr, &ca);
+}
+
+}  // namespace hfi
+
+extern "C" {
+
+int hf_batch_run_period_auto(hf_batch* b, const void* const* device_frames, const int* n_out, const float* t, void* const* device_out,
+                             int mode, const int32_t* force_kind) {
+    return batch_run_period_auto(b, device_frames, HF_MAX_PERIOD_OUTPUTS, n_out, t, device_out, mode, force_kind);
+}
+
+int hf_batch_run_period_auto_wide(hf_batch* b, const void* const* device_frames, int row, const int* n_out, const float* t,
+                                  void* const* device_out, int mode, const int32_t* force_kind) {
+    return batch_run_period_auto(b, device_frames, row, n_out, t, device_out, mode, force_kind);
 }
 
 int hf_batch_scene_read(hf_batch* b, int member, hf_scene_record* out, int capacity, int* n_records) {

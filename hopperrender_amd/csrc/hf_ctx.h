@@ -265,8 +265,8 @@ int batch_fail(hf_batch* b, int code, const std::string& msg);
 int batch_update(hf_batch* b, const void* const* device_frames, bool defer);
 int batch_check_flow_params(hf_batch* b);
 int batch_calculate(hf_batch* b, bool warmup_keeps_flow);
-int batch_interpolate(hf_batch* b, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
-                      bool convert_out = true);
+int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
+                      hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0);
 
 // hf_async_io.hip
 int io_init(hf_ctx* c);

@@ -251,7 +251,7 @@ int hf_batch_calculate_optical_flow(hf_batch* batch);
  * ONE launch. */
 int hf_batch_update_frames_device_ref(hf_batch* batch, const void* const* device_frames);
 /* hf_interpolate_period_ex(member i, NULL, n_out[i], t + 6 i, device_out + 6 i, mode, 0) for every member: the warps of
- * one source period of EVERY member in ONE launch (single-stream members, modes 0-2, every n_out[i] >= 1; otherwise
+ * one source period of EVERY member that has an output in ONE launch (single-stream members, modes 0-2; otherwise
  * member by member).  t and device_out are [batch size][HF_MAX_PERIOD_OUTPUTS] arrays; a NULL device_out entry
  * selects the member's internal output frame. */
 #define HF_MAX_PERIOD_OUTPUTS 6
@@ -322,6 +322,22 @@ int hf_batch_scene_set(hf_batch* batch, int member, int64_t source_frame_time, i
 int hf_batch_run_period_auto(hf_batch* batch, const void* const* device_frames, const int* n_out, const float* t, void* const* device_out,
                              int mode, const int32_t* force_kind);
 int hf_batch_scene_read(hf_batch* batch, int member, hf_scene_record* out, int capacity, int* n_records);
+/* ---- Periods of more than HF_MAX_PERIOD_OUTPUTS outputs (24 fps -> 144 Hz and above) ----
+ * The three period calls above with t and device_out as [batch size][row] arrays, 1 <= row <= HF_MAX_PERIOD_OUTPUTS_WIDE, and n_out[m] in
+ * [0, row]; the calls above are these with row = HF_MAX_PERIOD_OUTPUTS and keep refusing a seventh output.  Everything else -- NULL
+ * device_out entries, force_kind, n_out[m] == 0, the planar flags of the leader, the three-calls equivalence of hf_batch_run_period, what
+ * hf_batch_run_period_auto refuses and with which code -- is the narrow call's.  No new device code: a period goes out in chunks of up to
+ * HF_MAX_PERIOD_OUTPUTS outputs per member (chunk c = outputs [6 c, 6 c + 6), the split of hf_interpolate_period_ex), each chunk the fused
+ * launch over the members that have outputs in it, in the auto call followed by its predicated copy, under HF_FLAG_BATCH_PLANAR_OUT by its
+ * conversion launch; the decision and the scene record stay one per member and period, and a member never owns more than
+ * HF_MAX_PERIOD_OUTPUTS planar stages.  On a batch that defers its phase planes chunk 0 goes out ahead of the chain and builds the
+ * planes, the other chunks follow the chain.  Additive to ABI version 6. */
+#define HF_MAX_PERIOD_OUTPUTS_WIDE 24   /* 23.976 -> 480 Hz: 21 */
+int hf_batch_interpolate_period_wide(hf_batch* batch, int row, const int* n_out, const float* t, void* const* device_out, int mode);
+int hf_batch_run_period_wide(hf_batch* batch, const void* const* device_frames, int calculate_flow, int row, const int* n_out,
+                             const float* t, void* const* device_out, int mode);
+int hf_batch_run_period_auto_wide(hf_batch* batch, const void* const* device_frames, int row, const int* n_out, const float* t,
+                                  void* const* device_out, int mode, const int32_t* force_kind);
 int hf_batch_sync(hf_batch* batch);   /* hf_sync() of every member */
 int hf_batch_size(const hf_batch* batch);
 const char* hf_batch_last_error(const hf_batch* batch);   /* batch == NULL: error of the last failed hf_batch_create (per thread) */
