@@ -26,8 +26,9 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def chain_steps(f1, f2, g, R=16, delta=8, nb=6, iterations=0):
-    """Yields (level k, axis, window, offsets_before[2,lh,lw], offsets_after) for every step of the oracle's chain."""
+def chain_steps(f1, f2, g, R=16, delta=8, nb=6, iterations=0, with_sums=False):
+    """Yields (level k, axis, window, offsets_before[2,lh,lw], offsets_after) for every step of the oracle's chain; with_sums: and the
+    step's window sums [R,lh,lw] (a window's at its origin) and its count of samples outside the frame as a sixth and a seventh item."""
     L = oracle.lib()
     ws = L.hfo_initial_window(g.lw, g.lh)
     iters = L.hfo_iterations(ws, iterations)
@@ -36,11 +37,11 @@ def chain_steps(f1, f2, g, R=16, delta=8, nb=6, iterations=0):
     for k in range(iters):
         for axis in (0, 1):
             before = off.copy()
-            sums, _ = oracle.calc_delta_sums(f1, f2, off, g, ws, R, k, axis, delta, nb)
+            sums, oob = oracle.calc_delta_sums(f1, f2, off, g, ws, R, k, axis, delta, nb)
             sums = np.ascontiguousarray(sums)
             L.hfo_determine_lowest_layer(_p(sums), _p(lowest), ws, R, g.lh, g.lw)
             L.hfo_adjust_offsets(_p(off), _p(lowest), ws, R, g.lh, g.lw, axis)
-            yield k, axis, ws, before, off.copy()
+            yield (k, axis, ws, before, off.copy()) + ((sums, oob) if with_sums else ())
         ws = max(ws >> 1, 1)
 
 

@@ -21,7 +21,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chain_variant_model as M  # noqa: E402
-from chain_content import frames  # noqa: E402
+from chain_content import frames, kind_seed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -43,12 +43,12 @@ def _geom_key(case):
 
 def case_frames(case, kind):
     """Four consecutive frames of `kind` at the case's geometry (kept for the cases of one geometry: they follow each other in CASES)."""
-    gk = (case.hdr, case.H, case.W, case.in_stride)
+    gk = _geom_key(case)
     if _frame_cache.get("geometry") != gk:
         _frame_cache.clear()
         _frame_cache["geometry"] = gk
     if kind not in _frame_cache:
-        _frame_cache[kind] = frames(kind, case.H, case.W, bool(case.hdr), 9000 + 13 * KINDS.index(kind), 4, case.in_stride)
+        _frame_cache[kind] = frames(kind, case.H, case.W, bool(case.hdr), kind_seed(kind), 4, case.in_stride, M.geometry(case).rs)
     return _frame_cache[kind]
 
 
@@ -72,11 +72,11 @@ def oracle_results(case, pairs):
     return dict(zip(keys, _pool.map(lambda k: _oracle_chain(case, g, pairs[k][0], pairs[k][1], k), keys)))
 
 
-def make_members(case, n=None):
+def make_members(case, n=None, more_flags=0):
     from hopperrender_amd import capi
     from hopperrender_amd.calc import OpticalFlowCalcHDR, OpticalFlowCalcSDR
     cls = OpticalFlowCalcHDR if case.hdr else OpticalFlowCalcSDR
-    flags = capi.HF_FLAG_ASYNC | {M.ALWAYS: capi.HF_FLAG_SAD_REUSE_ALWAYS, M.NEVER: capi.HF_FLAG_NO_SAD_REUSE, M.DEFAULT: 0}[case.tables]
+    flags = capi.HF_FLAG_ASYNC | more_flags | {M.ALWAYS: capi.HF_FLAG_SAD_REUSE_ALWAYS, M.NEVER: capi.HF_FLAG_NO_SAD_REUSE, M.DEFAULT: 0}[case.tables]
     return [cls(case.H, case.W, case.in_stride, 0, case.delta, case.nb, 0.0, 255.0, case.max_res, iterations=case.iterations,
                 blur_radius=case.blur_radius, search_radius=case.R, flags=flags) for _ in range(case.n if n is None else n)]
 
@@ -108,11 +108,13 @@ def assert_table_counters(case, cc):
         assert lv["X"][0] == want[ws] and lv["Y"][0] == want[ws], (case.name, ws, lv, want[ws])
 
 
-def run_case(case):
+def run_case(case, kinds=None, more_flags=0):
+    """kinds: the content of each member (default: member_kinds);  more_flags: flags of every member beside the table mode's."""
     from hopperrender_amd.calc import FlowBatch
-    kinds = member_kinds(case.n)
+    kinds = member_kinds(case.n) if kinds is None else list(kinds)
+    assert len(kinds) == case.n
     fr = {k: case_frames(case, k) for k in dict.fromkeys(kinds)}
-    cs = make_members(case)
+    cs = make_members(case, more_flags=more_flags)
     b = None
     try:
         for c, k in zip(cs, kinds):
