@@ -65,68 +65,21 @@ int batch_check_flow_params(hf_batch* b) {
     return HF_OK;
 }
 
-// HF_FLAG_BATCH_PLANAR_OUT: the semi-planar frames the period's warps (and the predicated scene copy) write instead of the caller's
-// buffers -- period_stage of every member, grown to the largest n_out seen, kMaxWarpOutputs at the most: a wider period goes out in chunks
-// of that many outputs, each converted before the next one's warps reuse the stages (stream order).  Allocates, so a call runs it before
+// HF_FLAG_BATCH_PLANAR_OUT: every member's stages for its n_out (hf_calc.hip ensure_period_stages).  Allocates, so a call runs it before
 // its first enqueue; an n_out outside [0, row] is left to the check that reports it.
 int batch_ensure_out_stages(hf_batch* b, int row, const int* n_out) {
     if (!b->planar_out || !n_out) return HF_OK;
     if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    for (size_t m = 0; m < b->members.size(); m++) {
-        hf_ctx* c = b->members[m];
-        const int want = n_out[m] > row ? 0 : n_out[m] < hf::kMaxWarpOutputs ? n_out[m] : hf::kMaxWarpOutputs;
-        while ((int)c->period_stage.size() < want) {
-            void* p = nullptr;
-            if (hipMalloc(&p, c->out_bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "cannot allocate a planar output stage");
-            }
-            c->period_stage.push_back(p);
+    for (size_t m = 0; m < b->members.size(); m++)
+        if (ensure_period_stages(b->members[m], n_out[m] > row ? 0 : n_out[m])) {
+            (void)hipGetLastError();
+            return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "cannot allocate a planar output stage");
         }
-    }
     return HF_OK;
 }
 
-// The targets of one chunk of a period (hf_launch_plan.h plan_period_chunks): outs[m][i] is where output `first + i` of member m is written,
-// for i < count[m].  Plain batch: the caller's entry (NULL: the member's internal output frame).  HF_FLAG_BATCH_PLANAR_OUT: the member's
-// stage i where the caller named a buffer of its own, NULL (the internal frame, which stays semi-planar) where it did not.  After
-// batch_ensure_out_stages and the checks of n_out.
-void batch_chunk_targets(hf_batch* b, int row, int first, const uint8_t* count, void* const* device_out, void** outs) {
-    for (size_t m = 0; m < b->members.size(); m++)
-        for (int i = 0; i < count[m]; i++) {
-            void* o = device_out[m * (size_t)row + (size_t)(first + i)];
-            outs[m * hf::kMaxWarpOutputs + (size_t)i] = o && b->planar_out ? b->members[m]->period_stage[(size_t)i] : o;
-        }
-}
-
-// ... and behind the chunk's last launch: every staged output of every member into the caller's buffer, in ONE launch
-int batch_convert_chunk(hf_batch* b, int row, int first, const uint8_t* count, void* const* device_out, void* const* outs) {
-    hf::PlanarPair pairs[hf::kMaxPlanarOutPairs];
-    int np = 0;
-    for (size_t m = 0; m < b->members.size(); m++)
-        for (int i = 0; i < count[m]; i++) {
-            void* o = device_out[m * (size_t)row + (size_t)(first + i)];
-            if (o) pairs[np++] = hf::PlanarPair{outs[m * hf::kMaxWarpOutputs + (size_t)i], o};
-        }
-    if (!np) return HF_OK;
-    const hf::Geom& g = b->members[0]->g;
-    hf::launch_planar_out_batch(g.hdr, g.H, g.out_stride, np, pairs, b->stream);
-    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "planar output launch failed");
-    return HF_OK;
-}
-
-// The warps of one source period of every member, chunk by chunk (hf_launch_plan.h plan_period_chunks; a period of up to kMaxWarpOutputs
-// outputs per member is one chunk).  t and device_out are [batch size][row] arrays.  Per chunk: ONE fused launch over the members that have
-// outputs in it -- they keep their batch index wherever the device looks one up (scene_kinds, SceneCopyArgs) -- or, where that does not
-// qualify (diagnostic modes, odd shapes, a misaligned output, dual-stream members), those members one by one; behind it the predicated
-// copy of the chunk (copy != nullptr: hf_batch_run_period_auto; src and levels per member are the caller's, outputs and counts are filled
-// in here) and, under HF_FLAG_BATCH_PLANAR_OUT, the conversion of the chunk's staged outputs.  Stream order lets every chunk reuse the
-// same stages.  Chunks [first_chunk, ...) are issued.
-// before_chain (hf_batch_run_period with deferred phase planes): chunk 0 -- every member has outputs in it -- goes out AHEAD of the
-// period's chain: it reads frames N-2 / N-1 and the previous flow, which the chain does not touch, and builds the full plane of frame N-1
-// that the chain then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the
-// usual order.  The later chunks of the period always follow the chain (first_chunk = 1): the member-by-member path reads flow buffer 0,
-// which is the previous flow only once the chain has swapped the buffers.
+// The warps of one source period of every member: what a batch refuses, all of it before the first enqueue, then interpolate_period
+// (hf_calc.hip), which states before_chain, launched, copy and first_chunk.  t and device_out are [batch size][row] arrays.
 int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
                       hf::SceneCopyArgs* copy, int first_chunk) {
     if (launched) *launched = false;
@@ -138,77 +91,15 @@ int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, vo
     if (row < 1 || row > HF_MAX_PERIOD_OUTPUTS_WIDE)
         return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: row outside [1, " + std::to_string(HF_MAX_PERIOD_OUTPUTS_WIDE) + "]");
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    bool fused = !l->dual(), all_have = true;
     for (int m = 0; m < n; m++) {
         hf_ctx* c = b->members[m];
         if (!c) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "null context");
-        // batch members have no asynchronous host I/O (hf_batch_create / hf_*_async enforce it), so there is no output-ring slot to
-        // guard and no side stream to notify here -- the one-launch path relies on that
         if (c->io_in) return batch_fail(b, HF_ERR_STATE, "hf_batch_interpolate_period: a member uses asynchronous host I/O");
-        fused = fused && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
         if (int rc = check_period_args(c, "hf_batch_interpolate_period", n_out[m], row, t + (size_t)m * row, mode)) return batch_fail(b, rc, c->err);
-        all_have = all_have && n_out[m] >= 1;
     }
     if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;   // (the stages: allocated before anything of this call is enqueued)
-    const hf::PeriodChunks pc = hf::plan_period_chunks(n, n_out);
     static_assert(hf::kMaxPeriodOutputsWide == HF_MAX_PERIOD_OUTPUTS_WIDE && hf::kMaxWarpOutputs == HF_MAX_PERIOD_OUTPUTS, "the header's limits are the plan's");
-    if (before_chain && !(fused && all_have)) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
-    // (the auto call issues its predicated copy in a period without any output too: its launches do not depend on the schedule)
-    const int end = before_chain ? 1 : pc.n_chunks ? pc.n_chunks : copy ? 1 : 0;
-    for (int ch = first_chunk; ch < end; ch++) {
-        const uint8_t* count = pc.count[ch];
-        const int first = ch * hf::kMaxWarpOutputs;
-        void* outs[hf::kMaxPlanarOutPairs];
-        batch_chunk_targets(b, row, first, count, device_out, outs);
-        hf::WarpPeriod periods[hf::kMaxFlowBatch];
-        int who[hf::kMaxFlowBatch], np = 0, frames = 0;
-        for (int m = 0; m < n; m++) if (count[m]) { who[np++] = m; frames += count[m]; }
-        bool done = np == 0;
-        if (fused && np) {
-            // the chunk of every member in ONE launch on the batch stream (single-stream members: program order does the rest)
-            for (int k = 0; k < np; k++) {
-                const int m = who[k];
-                hf_ctx* c = b->members[m];
-                fill_period(c, count[m], t + (size_t)m * row + first, outs + (size_t)m * hf::kMaxWarpOutputs, periods[k], before_chain ? 1 : 0);
-                if (before_chain && c->plane_pending[1]) periods[k].plane21 = c->pp[1];
-                if (int rc = mark_warp_start(c, b->stream)) return batch_fail(b, rc, c->err);   // as in hf_warp_frames
-            }
-            const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
-            bool built[hf::kMaxFlowBatch];
-            if (hf::launch_warp_periods(l->g, np, periods, mode, b->stream, span >= 0 ? l->spans[span].b : nullptr, span >= 0 ? l->spans[span].e : nullptr,
-                                        before_chain ? &l->pl : nullptr, built)) {
-                if (span >= 0) l->spans[span].frames = frames;
-                if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
-                if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "fused warp launch failed");
-                for (int k = 0; k < np; k++) if (built[k]) b->members[who[k]]->plane_pending[1] = false;
-                done = true;
-            } else {
-                span_cancel(l, span);
-            }
-        }
-        if (!done) {
-            if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
-            for (int k = 0; k < np; k++) {    // not eligible (diagnostic modes, odd shapes, dual-stream members): member by member
-                const int m = who[k];
-                if (int rc = hf_interpolate_period_ex(b->members[m], nullptr, count[m], t + (size_t)m * row + first, outs + (size_t)m * hf::kMaxWarpOutputs, mode, 0))
-                    return batch_fail(b, rc, b->members[m]->err);
-            }
-        }
-        if (copy) {   // the repair of the cut periods: this chunk's outputs of the members whose kind is copy
-            for (int m = 0; m < n; m++) {
-                hf::SceneCopyArgs::Member& cm = copy->m[m];
-                cm.n_out = count[m];
-                for (int i = 0; i < count[m]; i++) {
-                    void* o = outs[(size_t)m * hf::kMaxWarpOutputs + (size_t)i];
-                    cm.outs[i] = o ? o : b->members[m]->out_frame;
-                }
-            }
-            hf::launch_scene_copy(l->g, *copy, b->scene_kinds, b->stream);
-            if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_copy launch failed");
-        }
-        if (b->planar_out) if (int rc = batch_convert_chunk(b, row, first, count, device_out, outs)) return rc;
-    }
-    return HF_OK;
+    return interpolate_period(b, b->members.data(), n, row, n_out, t, device_out, mode, before_chain, launched, copy, first_chunk);
 }
 
 // the launches a period of `chunks` chunks adds to a one-chunk period's: per further chunk up to two fused warp launches (17 members and
@@ -640,7 +531,7 @@ int batch_run_period_auto(hf_batch* b, const void* const* device_frames, int row
         da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
         hf::SceneCopyArgs::Member& cm = ca.m[m];
         const OutputLevels lv = output_levels(c);
-        cm.src = copy_source(c);          // (outputs and their number: per chunk, batch_interpolate)
+        cm.src = copy_source(c);          // (outputs and their number: per chunk, interpolate_period)
         cm.black = lv.black; cm.white = lv.white;
     }
     hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);

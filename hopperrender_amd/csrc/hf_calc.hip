@@ -364,20 +364,159 @@ OutputLevels output_levels(const hf_ctx* c) { const float k = c->g.hdr ? 256.0f 
 void* copy_source(const hf_ctx* c) { return c->ring[c->p.frame_count >= 3 ? 0 : c->p.frame_count >= 2 ? 1 : 2]; }
 
 // m_warpCalcTime (opticalFlowCalcSDR.cpp:36-41) runs from the first warp or copy launch after a download, on the stream the caller names
-int mark_warp_start(hf_ctx* c, hipStream_t s) {
+static int mark_warp_start(hf_ctx* c, hipStream_t s) {
     if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, s)); c->warp_started = true; }
     return HF_OK;
 }
 
 // Fills the period descriptor of one context: frames N-2 / N-1, the PREVIOUS flow (:154-156), levels, outputs.
 // flow_index 1: the period is issued BEFORE the chain of its source period -- the previous flow is still the newest one
-void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index) {
+static void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index = 0) {
     p.frame12 = c->ring[0]; p.frame21 = c->ring[1];
     p.flow = c->blurred[flow_index]; p.flow_xy = c->blurred_xy[flow_index];
     p.black = output_levels(c).black; p.white = output_levels(c).white;
     p.n_out = n;
     p.counters = c->counters;
     for (int i = 0; i < n; i++) { p.ts[i] = t[i]; p.outs[i] = outs[i] ? outs[i] : c->out_frame; }
+}
+
+// The semi-planar frames the warps of a period write where its output side is planar (HF_FLAG_PLANAR_OUT; a member of a
+// HF_FLAG_BATCH_PLANAR_OUT batch) and the caller named a buffer: grown to the widest period seen, kMaxWarpOutputs at the most -- a wider
+// period goes out in chunks, each converted before the next one's warps reuse the stages (stream order).  Allocates, so a call runs it
+// before its first enqueue.  Freed by hf_batch_destroy for a batch's members, by hf_destroy otherwise.
+int ensure_period_stages(hf_ctx* c, int n) {
+    while ((int)c->period_stage.size() < n && (int)c->period_stage.size() < hf::kMaxWarpOutputs) {
+        void* p = nullptr;
+        HF_HIP(c, hipMalloc(&p, c->out_bytes));
+        c->period_stage.push_back(p);
+    }
+    return HF_OK;
+}
+
+// The outputs of period p of ONE context on its warp stream: all of them in one launch when the fast warp kernel applies -- the flow is
+// looked up once and the source rows of the later outputs come from L1/L2 instead of HBM (2F + nF bytes instead of n * 3F) -- else one
+// launch per output.  Profiled launches carry start/stop events of the dispatch itself (hipExtLaunchKernel), i.e. the kernel's execution
+// time as rocprof reports it, not the time the launch spent queued behind other streams.  The caller records ev_warps_done.
+static int warp_member(hf_ctx* c, const hf::WarpPeriod& p, int mode) {
+    if (int rc = mark_warp_start(c, c->stream)) return rc;
+    if (int rc = enter_warp_stream(c)) return rc;
+    const int n_out = p.n_out;
+    for (int i = 0; i < n_out; i++) if (int rc = guard_output_slot(c, p.outs[i], c->warp_stream)) return rc;
+    const bool fuse = n_out >= 2 && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
+    bool fused = false;
+    if (fuse) {
+        const int span = span_open(c, 0);
+        fused = hf::launch_warp_periods(c->g, 1, &p, mode, c->warp_stream, span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
+        if (!fused) span_cancel(c, span);   // shape not eligible: drop the unused span
+        else if (span >= 0) c->spans[span].frames = n_out;
+    }
+    for (int i = 0; i < n_out && !fused; i++) {
+        const int span = span_open(c, 0);
+        hf::launch_warp(c->g, p.frame12, p.frame21, p.flow, p.flow_xy, p.outs[i], p.ts[i], mode, p.black, p.white, c->warp_stream,
+                        span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
+    }
+    HF_HIP(c, hipGetLastError());
+    return note_launch(c, c->warp_stream);
+}
+
+// The warps of one source period of n >= 1 contexts of one geometry, THE host path of a period's warps: a lone context (b == nullptr,
+// n == 1, any n_out) or the members of batch b.  t and device_out are [n][row] arrays.  Chunk by chunk (hf_launch_plan.h
+// period_chunk_count; a period of up to kMaxWarpOutputs outputs per member is one chunk), per chunk in stream order:
+//   1. targets: output i of a member goes to the caller's buffer, to the member's internal frame for a NULL entry, or -- planar output
+//      side and a buffer named -- to the member's stage i (ensure_period_stages: the caller's, with its checks of n_out);
+//   2. warps: ONE fused launch on the batch's stream over the members that have outputs in the chunk (single-stream members of a batch,
+//      none of them HF_FLAG_NO_FUSED_WARP; they keep their batch index wherever the device looks one up: scene_kinds, SceneCopyArgs) or,
+//      where that does not qualify (diagnostic modes, odd shapes, a misaligned output), those members one by one (warp_member);
+//   3. the predicated copy of the chunk (copy != nullptr: hf_batch_run_period_auto; src and levels per member are the caller's, outputs
+//      and counts are filled in here);
+//   4. the conversion of the chunk's staged outputs into the caller's planar buffers, in ONE launch on the stream its warps ran on.
+// Stream order lets every chunk reuse the same stages.  Chunks [first_chunk, ...) are issued.
+// before_chain (hf_batch_run_period with deferred phase planes): chunk 0 -- every member has outputs in it -- goes out AHEAD of the
+// period's chain: it reads frames N-2 / N-1 and the previous flow, which the chain does not touch, and builds the full plane of frame N-1
+// that the chain then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the
+// usual order.  The later chunks of the period always follow the chain (first_chunk = 1): the member-by-member path reads flow buffer 0,
+// which is the previous flow only once the chain has swapped the buffers.
+// An error is the failing context's (its err) and, of a batch, the batch's.
+int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int* n_out, const float* t, void* const* device_out, int mode,
+                       bool before_chain, bool* launched, hf::SceneCopyArgs* copy, int first_chunk) {
+    hf_ctx* l = cs[0];
+    const bool planar = b ? b->planar_out : l->planar_out();
+    auto of_member = [b](hf_ctx* m, int rc) { return b ? batch_fail(b, rc, m->err) : rc; };
+    auto of_launch = [b, l](const char* what) { return b ? batch_fail(b, HF_ERR_HIP, what) : fail(l, HF_ERR_HIP, "%s", what); };
+    bool fused = b && !l->dual(), all_have = true;
+    int chunks = 0;
+    for (int m = 0; m < n; m++) {
+        fused = fused && !(cs[m]->cfg.flags & HF_FLAG_NO_FUSED_WARP);
+        all_have = all_have && n_out[m] >= 1;
+        if (hf::period_chunks(n_out[m]) > chunks) chunks = hf::period_chunks(n_out[m]);
+    }
+    if (before_chain && !(fused && all_have)) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
+    // (the auto call issues its predicated copy in a period without any output too: its launches do not depend on the schedule)
+    const int end = before_chain ? 1 : chunks ? chunks : copy ? 1 : 0;
+    for (int ch = first_chunk; ch < end; ch++) {
+        hf::WarpPeriod periods[hf::kMaxFlowBatch];
+        hf::PlanarPair pairs[hf::kMaxPlanarOutPairs];
+        hf_ctx* who[hf::kMaxFlowBatch];
+        int np = 0, frames = 0, npairs = 0;
+        for (int m = 0; m < n; m++) {
+            hf_ctx* c = cs[m];
+            const int count = hf::period_chunk_count(n_out[m], ch);
+            const size_t at = (size_t)m * row + (size_t)ch * hf::kMaxWarpOutputs;
+            void* outs[hf::kMaxWarpOutputs];
+            for (int i = 0; i < count; i++) {
+                void* o = device_out[at + i];
+                outs[i] = o && planar ? c->period_stage[(size_t)i] : o;
+                if (o && planar) pairs[npairs++] = hf::PlanarPair{outs[i], o};
+            }
+            if (count) {
+                fill_period(c, count, t + at, outs, periods[np], before_chain ? 1 : 0);
+                who[np++] = c; frames += count;
+            }
+            if (copy) {   // the repair of the cut periods: this chunk's outputs of the members whose kind is copy
+                copy->m[m].n_out = count;
+                for (int i = 0; i < count; i++) copy->m[m].outs[i] = outs[i] ? outs[i] : c->out_frame;
+            }
+        }
+        bool done = np == 0;
+        if (fused && np) {
+            // the chunk of every member in ONE launch on the batch stream (single-stream members: program order does the rest).  They have
+            // no asynchronous host I/O (hf_batch_create / hf_*_async enforce it): no output-ring slot to guard, no side stream to notify
+            for (int k = 0; k < np; k++) {
+                hf_ctx* c = who[k];
+                if (before_chain && c->plane_pending[1]) periods[k].plane21 = c->pp[1];
+                if (int rc = mark_warp_start(c, l->stream)) return of_member(c, rc);
+            }
+            const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
+            bool built[hf::kMaxFlowBatch];
+            if (hf::launch_warp_periods(l->g, np, periods, mode, l->stream, span >= 0 ? l->spans[span].b : nullptr, span >= 0 ? l->spans[span].e : nullptr,
+                                        before_chain ? &l->pl : nullptr, built)) {
+                if (span >= 0) l->spans[span].frames = frames;
+                if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
+                if (hipGetLastError() != hipSuccess) return of_launch("fused warp launch failed");
+                for (int k = 0; k < np; k++) if (built[k]) who[k]->plane_pending[1] = false;
+                done = true;
+            } else {
+                span_cancel(l, span);
+            }
+        }
+        if (!done) {
+            if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
+            for (int k = 0; k < np; k++) if (int rc = warp_member(who[k], periods[k], mode)) return of_member(who[k], rc);
+        }
+        if (copy) {
+            hf::launch_scene_copy(l->g, *copy, b->scene_kinds, l->stream);
+            if (hipGetLastError() != hipSuccess) return of_launch("scene_copy launch failed");
+        }
+        if (npairs) {
+            hf::launch_planar_out_batch(l->g.hdr, l->g.H, l->g.out_stride, npairs, pairs, l->warp_stream);
+            if (hipGetLastError() != hipSuccess) return of_launch("planar output launch failed");
+        }
+    }
+    // one completion event for all the warps (and conversions) the period put on a member's warp stream, behind the last of them
+    for (int m = 0; m < n; m++)
+        if (n_out[m] > 0 && cs[m]->on_warp_stream)
+            if (hipEventRecord(cs[m]->ev_warps_done, cs[m]->warp_stream) != hipSuccess) return of_launch("hipEventRecord failed");
+    return HF_OK;
 }
 
 int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind) {
@@ -444,20 +583,10 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
     HF_CHECK_CTX(c);
     if (int rc = check_period_args(c, "warpFrames", 1, -1, &t, mode)) return rc;
     if (int rc = set_device(c)) return rc;
-    const OutputLevels lv = output_levels(c);
-    if (int rc = mark_warp_start(c, c->stream)) return rc;
-    if (int rc = enter_warp_stream(c)) return rc;
-    if (int rc = guard_output_slot(c, c->out_target, c->warp_stream)) return rc;
-    // frames N-2 / N-1 and the PREVIOUS flow (:154-156)
-    // profiled launches carry start/stop events of the dispatch itself (hipExtLaunchKernel), i.e. the kernel's
-    // execution time as rocprof reports it, not the time the launch spent queued behind other streams
-    const int span = span_open(c, 0);
-    hf::launch_warp(c->g, c->ring[0], c->ring[1], c->blurred[0], c->blurred_xy[0], c->out_target, t, mode,
-                    lv.black, lv.white, c->warp_stream,
-                    span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
-    if (c->on_warp_stream && !c->in_period) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
-    if (int rc = note_launch(c, c->warp_stream)) return rc;
-    HF_HIP(c, hipGetLastError());
+    hf::WarpPeriod p;   // frames N-2 / N-1 and the PREVIOUS flow (:154-156) into the output target
+    fill_period(c, 1, &t, &c->out_target, p);
+    if (int rc = warp_member(c, p, mode)) return rc;
+    if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
     return HF_OK;
 }
 
@@ -483,19 +612,9 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
                              int update_and_flow) {
     HF_CHECK_CTX(c);
     if (n_out < 0 || (n_out > 0 && (!t || !device_out))) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_interpolate_period: bad argument");
-    // HF_FLAG_PLANAR_OUT: the warps write semi-planar frames into stages of the context, converted into the caller's buffers at the end
-    std::vector<void*> staged;
-    void* const* const caller_out = device_out;
-    if (c->planar_out() && n_out > 0) {
+    if (c->planar_out() && n_out > 0) {   // (the stages: allocated before anything of this call is enqueued)
         if (int rc = set_device(c)) return rc;
-        while ((int)c->period_stage.size() < n_out) {
-            void* p = nullptr;
-            HF_HIP(c, hipMalloc(&p, c->out_bytes));
-            c->period_stage.push_back(p);
-        }
-        staged.assign(device_out, device_out + n_out);
-        for (int i = 0; i < n_out; i++) if (staged[i]) staged[i] = c->period_stage[(size_t)i];
-        device_out = staged.data();
+        if (int rc = ensure_period_stages(c, n_out)) return rc;
     }
     if (update_and_flow) {
         if (device_frame) if (int rc = hf_update_frame_device_ref(c, device_frame)) return rc;
@@ -504,51 +623,7 @@ int hf_interpolate_period_ex(hf_ctx* c, const void* device_frame, int n_out, con
     if (int rc = set_device(c)) return rc;
     // (only now: the three separate calls would have updated and calculated before warpFrames refused its arguments; n_out has no upper bound here)
     if (int rc = check_period_args(c, "hf_interpolate_period", n_out, -1, t, mode)) return rc;
-    // All outputs of the period in one launch when the fast warp kernel applies: the flow is looked up once and
-    // the source rows of the later outputs come from L1/L2 instead of HBM (2F + nF bytes instead of n * 3F).
-    const bool fuse = n_out >= 2 && !(c->cfg.flags & HF_FLAG_NO_FUSED_WARP);
-    int done = 0;
-    if (fuse) {
-        if (int rc = enter_warp_stream(c)) return rc;
-        while (done < n_out) {
-            const int n = n_out - done < hf::kMaxWarpOutputs ? n_out - done : hf::kMaxWarpOutputs;
-            hf::WarpPeriod p;
-            fill_period(c, n, t + done, device_out + done, p);
-            for (int i = 0; i < n; i++) if (int rc = guard_output_slot(c, p.outs[i], c->warp_stream)) return rc;
-            if (int rc = mark_warp_start(c, c->stream)) return rc;
-            const int span = span_open(c, 0);
-            const bool ok = hf::launch_warp_periods(c->g, 1, &p, mode, c->warp_stream,
-                                                    span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
-            if (!ok) {   // shape not eligible: drop the unused span and fall back to one launch per output
-                span_cancel(c, span);
-                break;
-            }
-            if (span >= 0) c->spans[span].frames = n;
-            HF_HIP(c, hipGetLastError());
-            done += n;
-        }
-        if (done > 0) {
-            if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
-            if (int rc = note_launch(c, c->warp_stream)) return rc;
-        }
-    }
-    void* const saved = c->out_target;
-    c->in_period = true;
-    int rc = HF_OK;
-    for (int i = done; i < n_out && rc == HF_OK; i++) {
-        c->out_target = device_out[i] ? device_out[i] : c->out_frame;
-        rc = hf_warp_frames(c, t[i], mode);
-    }
-    c->in_period = false;
-    c->out_target = saved;
-    if (rc == HF_OK && done < n_out && c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
-    if (rc == HF_OK && !staged.empty()) {   // behind the warps, on their stream
-        for (int i = 0; i < n_out; i++)
-            if (caller_out[i]) hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, staged[(size_t)i], caller_out[i], c->warp_stream);
-        HF_HIP(c, hipGetLastError());
-        if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
-    }
-    return rc;
+    return interpolate_period(nullptr, &c, 1, n_out, &n_out, t, device_out, mode);
 }
 
 int hf_download_frame(hf_ctx* c, void* host_out) {

@@ -4,7 +4,9 @@
 //                    statistics, profiling spans, parity taps, device-memory helpers
 //   hf_calc.hip      the five virtuals of one context: updateFrame, calculateOpticalFlow (the refinement chain as a cached hipGraph), warpFrames,
 //                    copyFrame, downloadFrame, and the fused period calls.  calculate_flow() there is the ONE host path of a chain, for n >= 1
-//                    contexts on a stream: hf_calculate_optical_flow is its n = 1 case, a batch's chain the same call on the batch's stream
+//                    contexts on a stream: hf_calculate_optical_flow is its n = 1 case, a batch's chain the same call on the batch's stream.
+//                    interpolate_period() there is the ONE host path of a source period's warps, for n >= 1 contexts chunk by chunk (targets,
+//                    fused or member-by-member warps, predicated copy, planar conversion): hf_interpolate_period is its n = 1 case
 //   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
 //                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
 //   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async / hf_download_frame_async, hf_wait_*)
@@ -83,7 +85,6 @@ struct hf_ctx {
     bool ev_flow_valid[2] = {false, false};
     bool dual() const { return (cfg.flags & HF_FLAG_DUAL_STREAM) != 0; }
     bool on_warp_stream = false;                       // warp stream currently ordered after `stream`
-    bool in_period = false;                            // inside hf_interpolate_period (one completion event for all its warps)
     std::string err;
 
     // public fields of the reference object (opticalFlowCalc.h:27-48)
@@ -144,8 +145,8 @@ struct hf_ctx {
     // planar frames at the boundary (HF_FLAG_PLANAR_IN / _OUT, hf_planar.hip); every buffer is allocated on first use
     void* in_stage[3] = {nullptr, nullptr, nullptr};             // planar host frames land here (rotates with ring_store / ev_slot_prep)
     void* out_stage[kOutRing] = {nullptr, nullptr, nullptr};     // planar frames the readbacks read ([i] paired with out_ring[i])
-    std::vector<void*> period_stage;                             // semi-planar targets of hf_interpolate_period's warps; of a member of a
-                                                                 // HF_FLAG_BATCH_PLANAR_OUT batch: of the batch's period warps
+    std::vector<void*> period_stage;                             // semi-planar targets of a period's warps where its output side is planar
+                                                                 // (ensure_period_stages: kMaxWarpOutputs at the most, reused chunk by chunk)
     bool planar_in() const { return (cfg.flags & HF_FLAG_PLANAR_IN) != 0; }
     bool planar_out() const { return (cfg.flags & HF_FLAG_PLANAR_OUT) != 0; }
 
@@ -256,8 +257,9 @@ int check_period_args(hf_ctx* c, const char* who, int n_out, int max_n_out, cons
 struct OutputLevels { float black, white; };
 OutputLevels output_levels(const hf_ctx* c);
 void* copy_source(const hf_ctx* c);
-int mark_warp_start(hf_ctx* c, hipStream_t s);
-void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index = 0);
+int ensure_period_stages(hf_ctx* c, int n);
+int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int* n_out, const float* t, void* const* device_out, int mode,
+                       bool before_chain = false, bool* launched = nullptr, hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0);
 int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind);
 
 // hf_batch.hip

@@ -287,13 +287,17 @@ inline WarpPlan plan_warp_periods(const Geom& g, int n, const WarpPeriod* period
     return P;
 }
 
-// A source period of more than kMaxWarpOutputs outputs (24 fps -> 144 Hz and above) is a few launches of the same kernels: the greedy split
-// hf_interpolate_period_ex uses, stated once for the batch paths (hf_batch.hip).  Chunk c of member m holds its outputs
-// [c * kMaxWarpOutputs, min((c + 1) * kMaxWarpOutputs, n_out[m])): every output in exactly one chunk, in order; chunk 0 holds every member
-// that has an output at all; n_chunks = ceil(max n_out / kMaxWarpOutputs), 0 when nobody has one.  An n_out outside
-// [0, kMaxPeriodOutputsWide] is clamped here and refused by the caller's argument checks.
+// A source period of more than kMaxWarpOutputs outputs (24 fps -> 144 Hz and above) is a few launches of the same kernels.  THE rule of the
+// split, for a lone context (any n_out) and a batch alike (hf_calc.hip interpolate_period): chunk c of a member holds its outputs
+// [c * kMaxWarpOutputs, min((c + 1) * kMaxWarpOutputs, n_out)) -- period_chunk_count of them: every output in exactly one chunk, in order;
+// chunk 0 holds every member that has an output at all; a period has period_chunks(largest n_out) chunks, none when nobody has an output.
+constexpr int period_chunk_count(int n_out, int c) {
+    return n_out - c * kMaxWarpOutputs < 0 ? 0 : n_out - c * kMaxWarpOutputs < kMaxWarpOutputs ? n_out - c * kMaxWarpOutputs : kMaxWarpOutputs;
+}
+constexpr int period_chunks(int n_out) { return n_out < 1 ? 0 : (n_out - 1) / kMaxWarpOutputs + 1; }
+// The rule as a table, for a batch's calls: an n_out outside [0, kMaxPeriodOutputsWide] is clamped here and refused by their argument checks.
 constexpr int kMaxPeriodOutputsWide = 24;   // HF_MAX_PERIOD_OUTPUTS_WIDE (23.976 fps -> 480 Hz: 21)
-constexpr int kMaxPeriodChunks = (kMaxPeriodOutputsWide + kMaxWarpOutputs - 1) / kMaxWarpOutputs;
+constexpr int kMaxPeriodChunks = period_chunks(kMaxPeriodOutputsWide);
 struct PeriodChunks {
     int n_chunks;
     uint8_t count[kMaxPeriodChunks][kMaxFlowBatch];   // outputs of member m in chunk c (0: the member sits the chunk out)
@@ -301,12 +305,9 @@ struct PeriodChunks {
 inline PeriodChunks plan_period_chunks(int n, const int* n_out) {
     PeriodChunks P{};
     for (int m = 0; m < n && m < kMaxFlowBatch; m++) {
-        const int total = n_out[m] < 0 ? 0 : n_out[m] > kMaxPeriodOutputsWide ? kMaxPeriodOutputsWide : n_out[m];
-        for (int c = 0; c * kMaxWarpOutputs < total; c++) {
-            const int left = total - c * kMaxWarpOutputs;
-            P.count[c][m] = (uint8_t)(left < kMaxWarpOutputs ? left : kMaxWarpOutputs);
-            if (c + 1 > P.n_chunks) P.n_chunks = c + 1;
-        }
+        const int total = n_out[m] > kMaxPeriodOutputsWide ? kMaxPeriodOutputsWide : n_out[m];
+        for (int c = 0; c < period_chunks(total); c++) P.count[c][m] = (uint8_t)period_chunk_count(total, c);
+        if (period_chunks(total) > P.n_chunks) P.n_chunks = period_chunks(total);
     }
     return P;
 }
