@@ -1,6 +1,7 @@
 // hopperrender_amd/csrc/hf_async_io.hip -- pinned asynchronous host I/O of a context on side streams (include/hopperflow.h
 // hf_update_frame_async / hf_download_frame_async, hf_wait_flow / hf_wait_download): the reference's blocking CL_TRUE transfers
-// (opticalFlowCalcSDR.cpp:19-42) as H2D / D2H copies that overlap the compute stream.  Layout of the ABI: hf_ctx.h.
+// (opticalFlowCalcSDR.cpp:19-42) as H2D / D2H copies that overlap the compute stream.  The upload is the H2D alone: the update behind it
+// is update_frames (hf_calc.hip), the host path of every update.  Layout of the ABI: hf_ctx.h.
 
 #include "hf_ctx.h"
 
@@ -73,22 +74,11 @@ int hf_update_frame_async(hf_ctx* c, const void* pinned_host_frame) {
     if (c->planar_in()) if (int rc = ensure_in_stage(c)) return rc;
     if (c->have_last_launch) HF_HIP(c, hipStreamWaitEvent(c->io_in, c->ev_last_launch, 0));
     HF_HIP(c, hipStreamWaitEvent(c->io_in, c->ev_slot_prep[0], 0));
-    HF_HIP(c, hipMemcpyAsync(c->planar_in() ? c->in_stage[0] : c->ring_store[0], pinned_host_frame, c->in_bytes, hipMemcpyHostToDevice, c->io_in));
+    void* const staged = c->planar_in() ? c->in_stage[0] : c->ring_store[0];
+    HF_HIP(c, hipMemcpyAsync(staged, pinned_host_frame, c->in_bytes, hipMemcpyHostToDevice, c->io_in));
     HF_HIP(c, hipEventRecord(c->ev_h2d, c->io_in));
-    if (int rc = leave_warp_stream(c)) return rc;
-    if (c->timing()) {
-        HF_HIP(c, hipEventRecord(c->ev_upload, c->stream));
-        c->upload_recorded = true;
-    }
-    HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
-    c->ring[0] = c->ring_store[0];
-    if (c->planar_in()) hf::launch_planar_in(c->g.hdr, c->g.H, c->g.in_stride, c->in_stage[0], c->ring[0], c->stream);
-    hf::launch_prep_frame(c->g, c->pl, c->ring[0], c->pp[0], c->stream);
-    c->plane_pending[0] = false;
-    HF_HIP(c, hipGetLastError());
-    HF_HIP(c, hipEventRecord(c->ev_slot_prep[0], c->stream));
-    rotate_after_upload(c);
-    return HF_OK;
+    // the update itself (hf_calc.hip update_frames): c->stream waits for ev_h2d instead of copying
+    return update_frames(nullptr, &c, 1, &staged, FrameSource::Staged, c->planar_in(), false, "hf_update_frame_async");
 }
 
 int hf_download_frame_async(hf_ctx* c, void* pinned_host_out) {

@@ -1,6 +1,7 @@
 // hopperrender_amd/csrc/hf_batch.hip -- hf_batch (include/hopperflow.h): up to 32 contexts of identical geometry and parameters issue their
 // phase planes, refinement chains and fused period warps as ONE set of launches on one stream (independent frame pairs);
-// results per member are those of the single-context calls of hf_calc.hip.  Layout of the ABI: hf_ctx.h.
+// results per member are those of the single-context calls of hf_calc.hip, whose host paths (update_frames, calculate_flow,
+// interpolate_period) issue them.  Here is what is a batch's own: argument checks, streams, timeline, scene state.  Layout of the ABI: hf_ctx.h.
 
 #include "hf_ctx.h"
 
@@ -15,43 +16,14 @@ int batch_fail(hf_batch* b, int code, const std::string& msg) {
     return code;
 }
 
-// defer: only the grid samples of the new frames now (what the chain of this period reads of them); their full planes are built by
-// the next period's warp launch or, failing that, by ensure_older_planes
+// hf_batch_update_frames_device_ref: update_frames (hf_calc.hip, which states defer) over the members, their frames referenced -- or, planar,
+// converted into the members' own slots
 int batch_update(hf_batch* b, const void* const* device_frames, bool defer) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     if (!device_frames) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_update_frames_device_ref: null argument");
-    hf_ctx* l = b->members[0];
-    const int n = (int)b->members.size();
-    if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    hf::PrepBatch pb{};
-    pb.n = n;
-    // first pass: everything that can fail, before any member's ring is touched (a failure leaves every member as it was)
-    for (int i = 0; i < n; i++) {
-        hf_ctx* m = b->members[i];
-        if (!device_frames[i]) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_update_frames_device_ref: null frame");
-        if (int rc = leave_warp_stream(m)) return batch_fail(b, rc, m->err);
-        if (m->timing() && hipEventRecord(m->ev_upload, b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipEventRecord failed");
-    }
-    hf::PlanarPair pin[hf::kMaxFlowBatch];
-    for (int i = 0; i < n; i++) {
-        hf_ctx* m = b->members[i];
-        if (m->timing()) m->upload_recorded = true;
-        if (b->planar_in) {   // converted into the member's own slot, as hf_update_frame_device_ref does under HF_FLAG_PLANAR_IN: no reference kept
-            m->ring[0] = m->ring_store[0];
-            pin[i] = hf::PlanarPair{device_frames[i], m->ring[0]};
-        } else {
-            m->ring[0] = const_cast<void*>(device_frames[i]);   // the ring references the caller's frame (hf_update_frame_device_ref)
-        }
-        pb.frame[i] = m->ring[0];
-        pb.pp[i] = m->pp[0];
-        m->plane_pending[0] = defer;
-    }
-    if (b->planar_in) hf::launch_planar_in_batch(l->g.hdr, l->g.H, l->g.in_stride, n, pin, b->stream);   // all new frames in one launch
-    if (defer) hf::launch_prep_grid(l->g, l->pl, pb, b->stream);
-    else hf::launch_prep_frames(l->g, l->pl, pb, b->stream);     // the phase planes of all new frames in one launch
-    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "phase-plane launch failed");
-    for (hf_ctx* m : b->members) rotate_after_upload(m);
-    return HF_OK;
+    if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
+    return update_frames(b, b->members.data(), (int)b->members.size(), device_frames, FrameSource::DeviceRef, b->planar_in, defer,
+                         "hf_batch_update_frames_device_ref");
 }
 
 // What hf_batch_calculate_optical_flow checks before it enqueues anything: valid flow parameters, equal in all members.

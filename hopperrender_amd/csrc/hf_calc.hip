@@ -1,6 +1,8 @@
 // hopperrender_amd/csrc/hf_calc.hip -- the five virtuals of ONE context on the gfx950 kernels (include/hopperflow.h): updateFrame
 // (opticalFlowCalcSDR.cpp:19-29), calculateOpticalFlow (:44-139; the 16-step refinement chain + blur as a cached hipGraph), warpFrames
-// (:141-168), copyFrame (:170-183), downloadFrame (:31-42), and the fused period calls built from them.  Layout of the ABI: hf_ctx.h.
+// (:141-168), copyFrame (:170-183), downloadFrame (:31-42), and the fused period calls built from them.  The three legs of a period each have
+// ONE host path here, for n >= 1 contexts: update_frames, calculate_flow, interpolate_period; a batch (hf_batch.hip) and the asynchronous
+// update (hf_async_io.hip) call the same functions.  Layout of the ABI: hf_ctx.h.
 
 #include "hf_ctx.h"
 
@@ -207,7 +209,7 @@ int leave_warp_stream(hf_ctx* c) {
     return HF_OK;
 }
 
-int rotate_after_upload(hf_ctx* c) {
+static void rotate_after_upload(hf_ctx* c) {
     // opticalFlowCalcSDR.cpp:22-28 : [0] <- [1] <- [2] <- new ; frame_count++
     void* f = c->ring[0];
     void* fs = c->ring_store[0];
@@ -223,39 +225,75 @@ int rotate_after_upload(hf_ctx* c) {
     c->ring[2] = f;          c->pp[2] = pp;       c->plane_pending[2] = pend;
     c->ring_phase = (c->ring_phase + 1) % 3;
     c->p.frame_count++;
-    return HF_OK;
 }
 
-// by_reference: the ring slot points at the caller's device frame instead of receiving a copy (not under HF_FLAG_PLANAR_IN: the
-// slot receives the converted frame)
-int update_common(hf_ctx* c, const void* src, hipMemcpyKind kind, bool by_reference) {
-    if (int rc = set_device(c)) return rc;
-    if (int rc = leave_warp_stream(c)) return rc;
-    if (c->timing()) {
-        HF_HIP(c, hipEventRecord(c->ev_upload, c->stream));  // m_ofcStartedEvent (:20)
+// The frame update of n >= 1 contexts of one geometry, THE host path of an update: a lone context (b == nullptr, n == 1) or the members of
+// batch b, each on its own c->stream (a batch's members share the batch's).  src[i] is context i's new frame, `how` the way all of them
+// arrive (FrameSource, hf_ctx.h), planar whether they are planar 4:2:0 (a context's HF_FLAG_PLANAR_IN, a batch's planar_in).  defer
+// (hf_batch_run_period): only the grid samples of the new frames now -- what the chain of this period reads of them; their full planes are
+// built by the next period's warp launch or, failing that, by ensure_older_planes.  In this order, each step for all n contexts:
+//   1. everything that can fail without enqueueing -- a null source (reported as `who`'s), leave_warp_stream, the stage of a planar host
+//      frame -- before any context's ring or flags are touched: a failure leaves every context as it was;
+//   2. ev_upload (m_ofcStartedEvent, opticalFlowCalcSDR.cpp:20) in front of everything the update enqueues;
+//   3. the frame: copied into the context's own slot (a planar host frame: into the slot's stage), waited for (Staged), or referenced.
+//      A planar frame always ends up in the own slot -- no reference is kept;
+//   4. ONE re-layout launch for all planar sources;  5. ONE phase-plane (or grid-sample) launch over all n;
+//   6. ev_slot_prep[0] for the side stream whose next H2D overwrites the slot or its stage;  7. the ring rotates;
+//   8. a lone blocking context waits for it all -- but not behind a Staged frame: nothing of asynchronous host I/O blocks (hopperflow.h).
+// An error is the failing context's (its err) and, of a batch, the batch's.
+int update_frames(hf_batch* b, hf_ctx* const* cs, int n, const void* const* src, FrameSource how, bool planar, bool defer, const char* who) {
+    hf_ctx* l = cs[0];
+    auto of_member = [b](hf_ctx* m, int rc) { return b ? batch_fail(b, rc, m->err) : rc; };
+    auto hip = [&](hf_ctx* m, hipError_t e, const char* what) -> int {
+        if (e == hipSuccess) return HF_OK;
+        return of_member(m, fail(m, e == hipErrorOutOfMemory ? HF_ERR_OUT_OF_MEMORY : HF_ERR_HIP, "HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what));
+    };
+    for (int i = 0; i < n; i++)
+        if (!src[i]) return b ? batch_fail(b, HF_ERR_INVALID_ARGUMENT, std::string(who) + ": null frame") : fail(cs[i], HF_ERR_INVALID_ARGUMENT, "%s: null frame", who);
+    for (int i = 0; i < n; i++) {
+        if (int rc = leave_warp_stream(cs[i])) return of_member(cs[i], rc);
+        if (planar && how == FrameSource::Host) if (int rc = ensure_in_stage(cs[i])) return of_member(cs[i], rc);
+    }
+    for (int i = 0; i < n; i++) {
+        hf_ctx* c = cs[i];
+        if (!c->timing()) continue;
+        if (int rc = hip(c, hipEventRecord(c->ev_upload, c->stream), "hipEventRecord")) return rc;
         c->upload_recorded = true;
     }
-    if (c->planar_in()) {
-        c->ring[0] = c->ring_store[0];
-        const void* planar = src;
-        if (kind == hipMemcpyHostToDevice) {   // one H2D of the whole frame into a stage, then the re-layout into the slot
-            if (int rc = ensure_in_stage(c)) return rc;
-            HF_HIP(c, hipMemcpyAsync(c->in_stage[0], src, c->in_bytes, kind, c->stream));
-            planar = c->in_stage[0];
+    hf::PrepBatch pb{};
+    hf::PlanarPair pin[hf::kMaxFlowBatch];
+    pb.n = n;
+    for (int i = 0; i < n; i++) {
+        hf_ctx* c = cs[i];
+        const bool by_reference = how == FrameSource::DeviceRef && !planar;
+        c->ring[0] = by_reference ? const_cast<void*>(src[i]) : c->ring_store[0];
+        const void* from = src[i];   // where the re-layout reads a planar frame
+        if (how == FrameSource::Staged) {   // the caller's H2D on io_in put it into the slot (planar: into the slot's stage, which is src[i])
+            if (int rc = hip(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0), "hipStreamWaitEvent")) return rc;
+        } else if (how == FrameSource::Host && planar) {   // one H2D of the whole frame into the stage
+            if (int rc = hip(c, hipMemcpyAsync(c->in_stage[0], src[i], c->in_bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync")) return rc;
+            from = c->in_stage[0];
+        } else if (!planar && !by_reference) {
+            const hipMemcpyKind kind = how == FrameSource::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+            if (int rc = hip(c, hipMemcpyAsync(c->ring[0], src[i], c->in_bytes, kind, c->stream), "hipMemcpyAsync")) return rc;
         }
-        hf::launch_planar_in(c->g.hdr, c->g.H, c->g.in_stride, planar, c->ring[0], c->stream);
-    } else if (by_reference) {
-        c->ring[0] = const_cast<void*>(src);
-    } else {
-        c->ring[0] = c->ring_store[0];
-        HF_HIP(c, hipMemcpyAsync(c->ring[0], src, c->in_bytes, kind, c->stream));
+        pin[i] = hf::PlanarPair{from, c->ring[0]};
+        pb.frame[i] = c->ring[0];
+        pb.pp[i] = c->pp[0];
+        c->plane_pending[0] = defer;
     }
-    hf::launch_prep_frame(c->g, c->pl, c->ring[0], c->pp[0], c->stream);
-    c->plane_pending[0] = false;
-    HF_HIP(c, hipGetLastError());
-    if (c->io_in) HF_HIP(c, hipEventRecord(c->ev_slot_prep[0], c->stream));
-    rotate_after_upload(c);
-    if (!c->async()) return sync_ctx(c);
+    // (a lone context keeps the single-frame kernel: its argument block is a tenth of the pair table's, 0.3 us per launch at 2160p)
+    if (planar && b) hf::launch_planar_in_batch(l->g.hdr, l->g.H, l->g.in_stride, n, pin, l->stream);
+    else if (planar) hf::launch_planar_in(l->g.hdr, l->g.H, l->g.in_stride, pin[0].src, pin[0].dst, l->stream);
+    if (defer) hf::launch_prep_grid(l->g, l->pl, pb, l->stream);
+    else hf::launch_prep_frames(l->g, l->pl, pb, l->stream);   // (non-temporal plane stores for n > 1 only: a lone context and a batch of one keep the cached variant)
+    if (int rc = hip(l, hipGetLastError(), "the phase-plane launch")) return rc;
+    for (int i = 0; i < n; i++) {
+        hf_ctx* c = cs[i];
+        if (c->io_in) if (int rc = hip(c, hipEventRecord(c->ev_slot_prep[0], c->stream), "hipEventRecord")) return rc;
+        rotate_after_upload(c);
+    }
+    if (!b && !l->async() && how != FrameSource::Staged) return sync_ctx(l);
     return HF_OK;
 }
 
@@ -550,25 +588,19 @@ int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind) {
 
 }  // namespace hfi
 
+static int update_one(hf_ctx* c, const void* frame, FrameSource how, const char* who) {
+    HF_CHECK_CTX(c);
+    if (int rc = set_device(c)) return rc;
+    return update_frames(nullptr, &c, 1, &frame, how, c->planar_in(), false, who);
+}
+
 extern "C" {
 
-int hf_update_frame(hf_ctx* c, const void* host_frame) {
-    HF_CHECK_CTX(c);
-    if (!host_frame) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_update_frame: null frame");
-    return update_common(c, host_frame, hipMemcpyHostToDevice);
-}
+int hf_update_frame(hf_ctx* c, const void* host_frame) { return update_one(c, host_frame, FrameSource::Host, "hf_update_frame"); }
 
-int hf_update_frame_device(hf_ctx* c, const void* device_frame) {
-    HF_CHECK_CTX(c);
-    if (!device_frame) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_update_frame_device: null frame");
-    return update_common(c, device_frame, hipMemcpyDeviceToDevice);
-}
+int hf_update_frame_device(hf_ctx* c, const void* device_frame) { return update_one(c, device_frame, FrameSource::Device, "hf_update_frame_device"); }
 
-int hf_update_frame_device_ref(hf_ctx* c, const void* device_frame) {
-    HF_CHECK_CTX(c);
-    if (!device_frame) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_update_frame_device_ref: null frame");
-    return update_common(c, device_frame, hipMemcpyDeviceToDevice, true);
-}
+int hf_update_frame_device_ref(hf_ctx* c, const void* device_frame) { return update_one(c, device_frame, FrameSource::DeviceRef, "hf_update_frame_device_ref"); }
 
 int hf_calculate_optical_flow(hf_ctx* c) {
     HF_CHECK_CTX(c);

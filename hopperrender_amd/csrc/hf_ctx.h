@@ -3,13 +3,16 @@
 //   hf_context.hip   context lifetime and state: hf_create / hf_destroy (detectDevices, buffers: opticalFlowCalcSDR.cpp:206-325), parameters,
 //                    statistics, profiling spans, parity taps, device-memory helpers
 //   hf_calc.hip      the five virtuals of one context: updateFrame, calculateOpticalFlow (the refinement chain as a cached hipGraph), warpFrames,
-//                    copyFrame, downloadFrame, and the fused period calls.  calculate_flow() there is the ONE host path of a chain, for n >= 1
+//                    copyFrame, downloadFrame, and the fused period calls.  update_frames() there is the ONE host path of a frame update, for
+//                    n >= 1 contexts: hf_update_frame / _device / _device_ref and, behind its own H2D, hf_update_frame_async are its n = 1
+//                    cases, a batch's update the same call over its members.  calculate_flow() there is the ONE host path of a chain, for n >= 1
 //                    contexts on a stream: hf_calculate_optical_flow is its n = 1 case, a batch's chain the same call on the batch's stream.
 //                    interpolate_period() there is the ONE host path of a source period's warps, for n >= 1 contexts chunk by chunk (targets,
 //                    fused or member-by-member warps, predicated copy, planar conversion): hf_interpolate_period is its n = 1 case
 //   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
 //                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
-//   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async / hf_download_frame_async, hf_wait_*)
+//   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async: the H2D, then update_frames;
+//                    hf_download_frame_async, hf_wait_*)
 //
 // Host orchestration restated from the reference's opticalFlowCalcSDR.cpp / opticalFlowCalcHDR.cpp (cited per function); the
 // architecture differs on purpose:
@@ -249,8 +252,10 @@ int ensure_older_planes(hf_ctx* const* cs, int n, hipStream_t s);
 void finish_flow_timing(hf_ctx* c);
 int enter_warp_stream(hf_ctx* c);
 int leave_warp_stream(hf_ctx* c);
-int rotate_after_upload(hf_ctx* c);
-int update_common(hf_ctx* c, const void* src, hipMemcpyKind kind, bool by_reference = false);
+// how the new frames of an update arrive: a host or device frame to copy, a device frame to reference, or a frame the caller's H2D on the
+// context's io_in stream has put into its slot already (ev_h2d recorded behind it)
+enum class FrameSource { Host, Device, DeviceRef, Staged };
+int update_frames(hf_batch* b, hf_ctx* const* cs, int n, const void* const* src, FrameSource how, bool planar, bool defer, const char* who);
 int check_flow_params(hf_ctx* c);
 int after_flow_enqueued(hf_ctx* c, hipStream_t s);
 int check_period_args(hf_ctx* c, const char* who, int n_out, int max_n_out, const float* t, int mode);

@@ -1490,12 +1490,6 @@ void launch_prep_grid(const Geom& g, const PhaseLayout& pl, const PrepBatch& b, 
     else HF_LAUNCH("grid_samples", (prep_grid_kernel<uint8_t>), grd, dim3(256), 0, stream, b, g.H, g.in_stride, pl, g.lw);
 }
 
-void launch_prep_frame(const Geom& g, const PhaseLayout& pl, const void* frame, uint32_t* pp, hipStream_t stream) {
-    PrepBatch b{};
-    b.n = 1; b.frame[0] = frame; b.pp[0] = pp;
-    launch_prep_frames(g, pl, b, stream);
-}
-
 // The plan's tile shapes (hf_launch_plan.h) are the device maps'.
 static_assert(plan_flow_level_small(1, 2, 16, false, false, false).tile_w == MapRow<2>::TW && plan_flow_level_small(1, 2, 16, false, false, false).waves == MapRow<2>::WAVES &&
               plan_flow_level_small(1, 4, 16, false, false, false).waves == MapRow<4>::WAVES && MapRow<4>::TW == 32, "row-per-lane tiles");

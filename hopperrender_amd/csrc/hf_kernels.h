@@ -138,9 +138,7 @@ struct BlurBatch {
     BlurItem s[kMaxFlowBatch];
 };
 
-// Re-lay a freshly uploaded frame as phase planes (once per frame).
-void launch_prep_frame(const Geom& g, const PhaseLayout& pl, const void* frame, uint32_t* pp, hipStream_t stream);
-// The same for n frames of one geometry in one launch (hf_batch).
+// Re-lay the freshly uploaded frames of n >= 1 contexts of one geometry as phase planes (once per frame) in one launch.
 struct PrepBatch {
     int n;
     const void* frame[kMaxFlowBatch];
