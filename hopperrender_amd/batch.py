@@ -106,8 +106,10 @@ def run_clips(batch, clips, source_frame_time=SOURCE_24, target_frame_time=TARGE
     one more per 128 periods, to hand the records out).  Any target rate up to 24 outputs per source period (24 fps -> 480 Hz is 21):
     periods of more than 6 outputs go through hf_batch_run_period_auto_wide, in chunks of 6 outputs per member on the device.
 
-    batch: a FlowBatch whose leader was created with HF_FLAG_BATCH_EAGER_PLANES (runPeriodAuto refuses a batch that defers
-    its phase planes); every member starts its clip here (m_frameCount is zeroed, the history re-armed).
+    batch: a FlowBatch; one that defers its phase planes (batch.defersPlanes(): frames above 1080p by default) needs
+    HF_FLAG_BATCH_AUTO_DEFERRED on its leader, which keeps the deferred order, or HF_FLAG_BATCH_EAGER_PLANES, which builds every plane when
+    its frame arrives -- runPeriodAuto raises the library's HF_ERR_STATE otherwise.  Every member starts its clip here (m_frameCount is
+    zeroed, the history re-armed).
     clips[i]: member i's source frames as device pointers, all clips of one length: NV12 / P010 frames in device memory, which
     must stay untouched until three further periods have been issued (the ring references them) -- or, for a batch whose leader
     carries HF_FLAG_BATCH_PLANAR_IN (batch.planar()[0]), planar yuv420p / yuv420p10le frames of the same size, each free as soon as

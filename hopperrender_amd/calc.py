@@ -404,7 +404,8 @@ class FlowBatch:
     def runPeriodAuto(self, dev_ptrs, scalars, out_ptrs, mode=BlendedFrame, force_kind=None):
         """hf_batch_run_period_auto: one source period of every member, warp or copy decided on the device; only enqueues.
         scalars[i] / out_ptrs[i]: member i's lists (an empty list: no output; more than 6 entries in some list:
-        hf_batch_run_period_auto_wide); force_kind: None or per member -1 decide / 0 copy / 1 warp."""
+        hf_batch_run_period_auto_wide); force_kind: None or per member -1 decide / 0 copy / 1 warp.  A batch that defers its phase planes
+        takes it with HF_FLAG_BATCH_AUTO_DEFERRED on its leader (the warps of chunk 0 stay ahead of the chain)."""
         prepared = self.preparePeriod(dev_ptrs, scalars, out_ptrs, mode)
         force = (C.c_int32 * len(self.members))(*[int(k) for k in force_kind]) if force_kind is not None else None
         if len(prepared) == 6:

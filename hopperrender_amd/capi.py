@@ -23,6 +23,7 @@ HF_FLAG_PLANAR_IN = 0x8000      # frames handed to the context are planar 4:2:0 
 HF_FLAG_PLANAR_OUT = 0x10000    # frames handed back are planar 4:2:0
 HF_FLAG_BATCH_PLANAR_IN = 0x20000    # on a batch's leader: the batch's input frames are planar 4:2:0
 HF_FLAG_BATCH_PLANAR_OUT = 0x40000   # on a batch's leader: the batch's caller-owned outputs are planar 4:2:0
+HF_FLAG_BATCH_AUTO_DEFERRED = 0x80000  # on a batch's leader: runPeriodAuto accepts a batch that defers its phase planes and keeps the deferred order
 HF_MAX_PERIOD_OUTPUTS = 6
 HF_MAX_PERIOD_OUTPUTS_WIDE = 24   # the *_wide period calls: 23.976 fps -> 480 Hz is 21 outputs per source period
 

@@ -51,9 +51,9 @@ int batch_ensure_out_stages(hf_batch* b, int row, const int* n_out) {
 }
 
 // The warps of one source period of every member: what a batch refuses, all of it before the first enqueue, then interpolate_period
-// (hf_calc.hip), which states before_chain, launched, copy and first_chunk.  t and device_out are [batch size][row] arrays.
+// (hf_calc.hip), which states before_chain, launched, copy, first_chunk and first_parts.  t and device_out are [batch size][row] arrays.
 int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
-                      hf::SceneCopyArgs* copy, int first_chunk) {
+                      hf::SceneCopyArgs* copy, int first_chunk, int first_parts) {
     if (launched) *launched = false;
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
     if (!n_out || !t || !device_out) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_interpolate_period: null argument");
@@ -71,7 +71,7 @@ int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, vo
     }
     if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;   // (the stages: allocated before anything of this call is enqueued)
     static_assert(hf::kMaxPeriodOutputsWide == HF_MAX_PERIOD_OUTPUTS_WIDE && hf::kMaxWarpOutputs == HF_MAX_PERIOD_OUTPUTS, "the header's limits are the plan's");
-    return interpolate_period(b, b->members.data(), n, row, n_out, t, device_out, mode, before_chain, launched, copy, first_chunk);
+    return interpolate_period(b, b->members.data(), n, row, n_out, t, device_out, mode, before_chain, launched, copy, first_chunk, first_parts);
 }
 
 // the launches a period of `chunks` chunks adds to a one-chunk period's: per further chunk up to two fused warp launches (17 members and
@@ -190,6 +190,8 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     // at update time.
     b->defer_planes = !l->dual() && !(l->cfg.flags & HF_FLAG_BATCH_EAGER_PLANES) && hf::warp_period_can_build_planes(l->g, l->pl, n);
     for (int i = 0; i < n; i++) b->defer_planes = b->defer_planes && !(members[i]->cfg.flags & HF_FLAG_NO_FUSED_WARP);
+    // ... and hf_batch_run_period_auto keeps that order where the leader asks for it (hf_launch_plan.h plan_auto_period)
+    b->auto_deferred = b->defer_planes && (l->cfg.flags & HF_FLAG_BATCH_AUTO_DEFERRED) != 0;
     b->planar_in = planar_in;
     b->planar_out = planar_out;
     *out = b;
@@ -460,7 +462,7 @@ int batch_run_period_auto(hf_batch* b, const void* const* device_frames, int row
     if (int rc = check_period_args(l, "hf_batch_run_period_auto", 0, -1, nullptr, mode)) return batch_fail(b, rc, l->err);
     if (row < 1 || row > HF_MAX_PERIOD_OUTPUTS_WIDE)
         return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_run_period_auto: row outside [1, " + std::to_string(HF_MAX_PERIOD_OUTPUTS_WIDE) + "]");
-    if (b->defer_planes)
+    if (b->defer_planes && !b->auto_deferred)
         return batch_fail(b, HF_ERR_STATE, "hf_batch_run_period_auto: this batch defers its phase planes, so a period's warps are issued ahead of its chain and the "
                                            "decision does not exist yet; create the leader with HF_FLAG_BATCH_EAGER_PLANES");
     if (l->dual())
@@ -482,35 +484,70 @@ int batch_run_period_auto(hf_batch* b, const void* const* device_frames, int row
     if (int rc = batch_check_flow_params(b)) return rc;
     // HF_FLAG_BATCH_PLANAR_OUT: warps and the predicated copy write the stages; one conversion launch behind both, per chunk
     if (int rc = batch_ensure_out_stages(b, row, n_out)) return rc;
-    ObserverGuard observer_guard(b, hf::plan_period_chunks(n, n_out).n_chunks);
-    if (int rc = batch_update(b, device_frames, false)) return rc;
-    if (int rc = batch_calculate(b, true)) return rc;
-    // the decision, behind the chain's last launch
-    hf::SceneDecideArgs da{};
+    const int chunks = hf::plan_period_chunks(n, n_out).n_chunks;
+    ObserverGuard observer_guard(b, chunks);
+    // a batch that defers its planes (and whose leader carries HF_FLAG_BATCH_AUTO_DEFERRED: the others were refused above) samples only the
+    // grid of the new frames, as hf_batch_run_period does
+    if (int rc = batch_update(b, device_frames, b->auto_deferred)) return rc;
+    bool pending = false, all_have = true;
+    for (int m = 0; m < n; m++) {
+        pending = pending || b->members[m]->plane_pending[1];
+        all_have = all_have && n_out[m] >= 1;
+    }
+    // the copy's arguments that do not depend on the chunk (outputs and their number: per chunk, interpolate_period); the ring is the update's
     hf::SceneCopyArgs ca{};
-    da.n = ca.n = n;
+    ca.n = n;
     for (int m = 0; m < n; m++) {
         hf_ctx* c = b->members[m];
-        hf_batch::SceneMember& sm = b->scene[(size_t)m];
-        const uint32_t fc = c->p.frame_count;   // m_frameCount of this period (the update has counted the new frame)
-        da.total_delta[m] = c->d_total_delta;
-        da.frame_count[m] = fc;
-        da.threshold[m] = sm.threshold;
-        da.slot[m] = (uint32_t)(sm.written % hf_batch::kSceneRing);
-        da.cap[m] = (int8_t)sm.cap;
-        da.push[m] = fc >= 3 ? 1 : 0;           // HopperRender.cpp:955-972
-        da.clear[m] = sm.clear ? 1 : 0;
-        da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
-        hf::SceneCopyArgs::Member& cm = ca.m[m];
         const OutputLevels lv = output_levels(c);
-        cm.src = copy_source(c);          // (outputs and their number: per chunk, interpolate_period)
-        cm.black = lv.black; cm.white = lv.white;
+        ca.m[m].src = copy_source(c);
+        ca.m[m].black = lv.black; ca.m[m].white = lv.white;
     }
-    hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
-    if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
-    for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
-    // the unchanged warps of the period (diagnostic modes: member by member on the same stream) and the repair of the cut periods, chunk by chunk
-    return batch_interpolate(b, row, n_out, t, device_out, mode, false, nullptr, &ca);
+    // The period's order is hf_launch_plan.h's.  The steps behind the decision are chunk 0's -- all three launches, or only its copy and
+    // conversion where its warps went ahead -- and then the later chunks whole: one interpolate_period call, first_parts says which of chunk 0.
+    hf::AutoPeriodPlan plan = hf::plan_auto_period(b->defer_planes, b->auto_deferred, pending, mode, all_have, chunks);
+    for (int k = 0; k < plan.n_steps; k++) {
+        const hf::PeriodStep step = plan.step[k];
+        if (step.kind == hf::kStepEarlyWarps) {
+            // The warps of chunk 0 and nothing else of it: they read frames N-2 / N-1 and the flow buffer that is blurred[0] once the chain has
+            // swapped (a warm-up member: the buffer its chain does not write; its outputs are overwritten by the copy), and build the pending
+            // planes.  Nothing enqueued (the one-launch plan does not qualify): the period takes the usual order and the chain's stand-alone
+            // plane launch fills in; a launch that was enqueued and failed is final.
+            bool warped = false;
+            const int rc = batch_interpolate(b, row, n_out, t, device_out, mode, true, &warped, nullptr, 0, hf::kPartWarps);
+            if (warped) { if (rc) return rc; continue; }
+            plan = hf::plan_auto_period(b->defer_planes, false, pending, mode, all_have, chunks);
+            k = -1;
+        } else if (step.kind == hf::kStepChain) {
+            if (int rc = batch_calculate(b, true)) return rc;
+        } else if (step.kind == hf::kStepDecide) {   // behind the chain's last launch
+            hf::SceneDecideArgs da{};
+            da.n = n;
+            for (int m = 0; m < n; m++) {
+                hf_ctx* c = b->members[m];
+                hf_batch::SceneMember& sm = b->scene[(size_t)m];
+                const uint32_t fc = c->p.frame_count;   // m_frameCount of this period (the update has counted the new frame)
+                da.total_delta[m] = c->d_total_delta;
+                da.frame_count[m] = fc;
+                da.threshold[m] = sm.threshold;
+                da.slot[m] = (uint32_t)(sm.written % hf_batch::kSceneRing);
+                da.cap[m] = (int8_t)sm.cap;
+                da.push[m] = fc >= 3 ? 1 : 0;           // HopperRender.cpp:955-972
+                da.clear[m] = sm.clear ? 1 : 0;
+                da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
+            }
+            hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
+            if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
+            for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
+        } else {
+            // the unchanged warps of the period (diagnostic modes: member by member on the same stream) and the repair of the cut periods, chunk by chunk
+            int first_parts = 0;
+            for (int j = k; j < plan.n_steps; j++)
+                if (plan.step[j].chunk == 0) first_parts |= plan.step[j].kind == hf::kStepWarps ? hf::kPartWarps : plan.step[j].kind == hf::kStepCopy ? hf::kPartCopy : hf::kPartConvert;
+            return batch_interpolate(b, row, n_out, t, device_out, mode, false, nullptr, &ca, 0, first_parts);
+        }
+    }
+    return HF_OK;
 }
 
 }  // namespace hfi

@@ -468,15 +468,19 @@ static int warp_member(hf_ctx* c, const hf::WarpPeriod& p, int mode) {
 //   3. the predicated copy of the chunk (copy != nullptr: hf_batch_run_period_auto; src and levels per member are the caller's, outputs
 //      and counts are filled in here);
 //   4. the conversion of the chunk's staged outputs into the caller's planar buffers, in ONE launch on the stream its warps ran on.
-// Stream order lets every chunk reuse the same stages.  Chunks [first_chunk, ...) are issued.
+// Stream order lets every chunk reuse the same stages.  Chunks [first_chunk, ...) are issued; of chunk first_chunk only the launches named in
+// first_parts (hf_launch_plan.h PeriodParts), of the later chunks all three.
 // before_chain (hf_batch_run_period with deferred phase planes): chunk 0 -- every member has outputs in it -- goes out AHEAD of the
 // period's chain: it reads frames N-2 / N-1 and the previous flow, which the chain does not touch, and builds the full plane of frame N-1
 // that the chain then reads.  Only the one-launch path qualifies; *launched = false means nothing was enqueued and the caller keeps the
 // usual order.  The later chunks of the period always follow the chain (first_chunk = 1): the member-by-member path reads flow buffer 0,
-// which is the previous flow only once the chain has swapped the buffers.
+// which is the previous flow only once the chain has swapped the buffers.  hf_batch_run_period_auto on a deferring batch (hf_launch_plan.h
+// plan_auto_period) sends only the WARPS of chunk 0 ahead (before_chain, first_parts = kPartWarps) and issues that chunk's copy and
+// conversion behind the decision (first_chunk = 0, first_parts = kPartCopy | kPartConvert): the targets of a chunk depend on the call's
+// arguments alone, so both calls name the same stages, which nothing between them touches.
 // An error is the failing context's (its err) and, of a batch, the batch's.
 int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int* n_out, const float* t, void* const* device_out, int mode,
-                       bool before_chain, bool* launched, hf::SceneCopyArgs* copy, int first_chunk) {
+                       bool before_chain, bool* launched, hf::SceneCopyArgs* copy, int first_chunk, int first_parts) {
     hf_ctx* l = cs[0];
     const bool planar = b ? b->planar_out : l->planar_out();
     auto of_member = [b](hf_ctx* m, int rc) { return b ? batch_fail(b, rc, m->err) : rc; };
@@ -495,6 +499,7 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
         hf::WarpPeriod periods[hf::kMaxFlowBatch];
         hf::PlanarPair pairs[hf::kMaxPlanarOutPairs];
         hf_ctx* who[hf::kMaxFlowBatch];
+        const int parts = ch == first_chunk ? first_parts : hf::kPartsAll;
         int np = 0, frames = 0, npairs = 0;
         for (int m = 0; m < n; m++) {
             hf_ctx* c = cs[m];
@@ -515,8 +520,8 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
                 for (int i = 0; i < count; i++) copy->m[m].outs[i] = outs[i] ? outs[i] : c->out_frame;
             }
         }
-        bool done = np == 0;
-        if (fused && np) {
+        bool done = np == 0 || !(parts & hf::kPartWarps);
+        if (fused && !done) {
             // the chunk of every member in ONE launch on the batch stream (single-stream members: program order does the rest).  They have
             // no asynchronous host I/O (hf_batch_create / hf_*_async enforce it): no output-ring slot to guard, no side stream to notify
             for (int k = 0; k < np; k++) {
@@ -541,11 +546,11 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
             if (before_chain) return HF_OK;   // not eligible for one launch: the caller issues the period after the chain, as usual
             for (int k = 0; k < np; k++) if (int rc = warp_member(who[k], periods[k], mode)) return of_member(who[k], rc);
         }
-        if (copy) {
+        if (copy && (parts & hf::kPartCopy)) {
             hf::launch_scene_copy(l->g, *copy, b->scene_kinds, l->stream);
             if (hipGetLastError() != hipSuccess) return of_launch("scene_copy launch failed");
         }
-        if (npairs) {
+        if (npairs && (parts & hf::kPartConvert)) {
             hf::launch_planar_out_batch(l->g.hdr, l->g.H, l->g.out_stride, npairs, pairs, l->warp_stream);
             if (hipGetLastError() != hipSuccess) return of_launch("planar output launch failed");
         }

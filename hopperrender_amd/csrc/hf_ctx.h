@@ -209,6 +209,7 @@ struct hf_batch {
     hipStream_t stream = nullptr;           // the batch's own (highest-priority) stream, shared by all members while the batch exists
     ChainGraphs graphs;
     bool defer_planes = false;              // hf_batch_run_period: grid samples at update, full plane of frame N-1 from the warp launch
+    bool auto_deferred = false;             // ... and hf_batch_run_period_auto too: the leader's HF_FLAG_BATCH_AUTO_DEFERRED on a batch that defers
     // planar 4:2:0 frames at the batch's boundary (the leader's HF_FLAG_BATCH_PLANAR_IN / _OUT; hf_planar.hip): new frames are converted
     // into the members' ring slots, caller-owned outputs out of the members' period_stage frames, by one launch each
     bool planar_in = false, planar_out = false;
@@ -264,7 +265,8 @@ OutputLevels output_levels(const hf_ctx* c);
 void* copy_source(const hf_ctx* c);
 int ensure_period_stages(hf_ctx* c, int n);
 int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int* n_out, const float* t, void* const* device_out, int mode,
-                       bool before_chain = false, bool* launched = nullptr, hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0);
+                       bool before_chain = false, bool* launched = nullptr, hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0,
+                       int first_parts = hf::kPartsAll);
 int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind);
 
 // hf_batch.hip
@@ -273,7 +275,7 @@ int batch_update(hf_batch* b, const void* const* device_frames, bool defer);
 int batch_check_flow_params(hf_batch* b);
 int batch_calculate(hf_batch* b, bool warmup_keeps_flow);
 int batch_interpolate(hf_batch* b, int row, const int* n_out, const float* t, void* const* device_out, int mode, bool before_chain, bool* launched,
-                      hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0);
+                      hf::SceneCopyArgs* copy = nullptr, int first_chunk = 0, int first_parts = hf::kPartsAll);
 
 // hf_async_io.hip
 int io_init(hf_ctx* c);

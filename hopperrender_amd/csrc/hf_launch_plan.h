@@ -312,6 +312,40 @@ inline PeriodChunks plan_period_chunks(int n, const int* n_out) {
     return P;
 }
 
+// The order of one hf_batch_run_period_auto period behind its update (hf_batch.hip batch_run_period_auto follows it step by step).  Every
+// chunk has three launches -- its warps, the predicated copy of the members whose period turned out to be a cut, under a planar output side
+// its conversion -- in that order; the copy needs the decision, which needs the chain.  The warps need neither, so on a batch that defers
+// its phase planes (defers) and whose leader asked for it (flag: HF_FLAG_BATCH_AUTO_DEFERRED) the warps of chunk 0 go out AHEAD of the chain
+// and build the planes the chain reads, exactly where hf_batch_run_period sends them ahead: some member's older plane still lacks its full
+// build (pending), a warp mode (0 .. 2), every member has an output -- chunk 0 then holds every member.  Its copy and conversion wait for
+// the decision; the later chunks are whole.  In every other case: chain, decision, then chunk by chunk.  chunks: plan_period_chunks'
+// n_chunks; a period without any output still has its one (empty) chunk, whose copy launch goes out as it always has.  A launch that has
+// nothing to do in a period (no planar output, no member with outputs in the chunk) is skipped by the host, not by the plan.
+enum PeriodStepKind { kStepEarlyWarps = 0, kStepChain = 1, kStepDecide = 2, kStepWarps = 3, kStepCopy = 4, kStepConvert = 5 };
+struct PeriodStep { uint8_t kind, chunk; };
+constexpr int kMaxAutoPeriodSteps = 2 + 3 * kMaxPeriodChunks;
+struct AutoPeriodPlan {
+    int n_steps;
+    int early;                              // chunk 0's warps are the first step
+    PeriodStep step[kMaxAutoPeriodSteps];
+};
+constexpr AutoPeriodPlan plan_auto_period(bool defers, bool flag, bool pending, int mode, bool all_have, int chunks) {
+    AutoPeriodPlan P{};
+    const int n_chunks = chunks < 1 ? 1 : chunks > kMaxPeriodChunks ? kMaxPeriodChunks : chunks;
+    P.early = defers && flag && pending && mode >= 0 && mode <= 2 && all_have && chunks >= 1;
+    if (P.early) P.step[P.n_steps++] = PeriodStep{kStepEarlyWarps, 0};
+    P.step[P.n_steps++] = PeriodStep{kStepChain, 0};
+    P.step[P.n_steps++] = PeriodStep{kStepDecide, 0};
+    for (int c = 0; c < n_chunks; c++) {
+        if (!(P.early && c == 0)) P.step[P.n_steps++] = PeriodStep{kStepWarps, (uint8_t)c};
+        P.step[P.n_steps++] = PeriodStep{kStepCopy, (uint8_t)c};
+        P.step[P.n_steps++] = PeriodStep{kStepConvert, (uint8_t)c};
+    }
+    return P;
+}
+// which of a chunk's three launches a call of interpolate_period (hf_calc.hip) issues
+enum PeriodParts { kPartWarps = 1, kPartCopy = 2, kPartConvert = 4, kPartsAll = 7 };
+
 // warp_kernel / copy_kernel <E, 16 / sizeof(E), aligned>: 16-byte stores, 256-thread workgroups.
 struct PlanePassPlan {
     int aligned;

@@ -99,6 +99,14 @@ typedef enum hf_output_mode {
  * context's own calls ignore them and the members stay ordinary NV12 / P010 contexts (see hf_batch_create). */
 #define HF_FLAG_BATCH_PLANAR_IN 0x20000  /* the batch's input frames are planar */
 #define HF_FLAG_BATCH_PLANAR_OUT 0x40000 /* the batch's caller-owned outputs are planar */
+#define HF_FLAG_BATCH_AUTO_DEFERRED 0x80000 /* on the leader passed to hf_batch_create: hf_batch_run_period_auto(_wide) accepts a batch that defers its
+                                             * phase planes (hf_batch_defers_planes) and keeps the deferred order -- grid samples at update time, the
+                                             * warps of the period's first six outputs per member ahead of its chain, where they build the planes; only
+                                             * the predicated copy and the planar conversion of those outputs wait for the decision.  Same outputs,
+                                             * records and state as the HF_FLAG_BATCH_EAGER_PLANES twin.  No effect on a batch that does not defer, on
+                                             * hf_batch_run_period and the three separate calls, on the HF_FLAG_DUAL_STREAM refusal.  Without it the
+                                             * auto call refuses a deferring batch, as ABI 6 documents; the flag becomes the default at the next ABI
+                                             * bump.  Additive to ABI version 6. */
 /* (0x10, 0x20, 0x100, 0x400 were round-1 stream-topology experiments -- shared warp stream, priority streams, warp
  *  turnstile, deferred phase planes -- all measured slower or equal; removed, findings in DESIGN.md section 4) */
 
@@ -306,9 +314,19 @@ int hf_batch_planar(const hf_batch* batch);
  *                             n_out[m] == 0 writes nothing for member m; its history still advances.  Any output mode (diagnostic modes
  *                             warp member by member on the same stream).  Every period of an armed member must go through this call: the
  *                             history assumes consecutive m_frameCount values (re-arm after anything else).
- *                             HF_ERR_STATE, nothing enqueued: a batch that defers its phase planes (hf_batch_defers_planes: the period's
- *                             warps are issued ahead of its chain there -- create the leader with HF_FLAG_BATCH_EAGER_PLANES),
- *                             HF_FLAG_DUAL_STREAM members, a member that was never armed, a record ring that would overflow.
+ *                             HF_ERR_STATE, nothing enqueued: a batch that defers its phase planes (hf_batch_defers_planes) whose leader
+ *                             carries neither HF_FLAG_BATCH_AUTO_DEFERRED nor HF_FLAG_BATCH_EAGER_PLANES, HF_FLAG_DUAL_STREAM members, a
+ *                             member that was never armed, a record ring that would overflow.
+ *                             On a deferring batch with HF_FLAG_BATCH_AUTO_DEFERRED the period keeps hf_batch_run_period's order: the update
+ *                             samples only the grid, and where that call would send chunk 0 ahead (some member's older plane pending, mode
+ *                             0 .. 2, every member has an output, the one-launch warp qualifies) its WARPS go out ahead of the chain and
+ *                             build the planes; chain and decision follow; then chunk 0's predicated copy and planar conversion, then the
+ *                             later chunks whole.  Every other period takes the order above and the chain's stand-alone plane launch fills
+ *                             in.  Everything a host can observe equals the HF_FLAG_BATCH_EAGER_PLANES twin (a member whose m_frameCount is
+ *                             below 3 is warped early with the flow buffer its chain does not write, and then overwritten by the copy; only
+ *                             force_kind 1 on such a member, whose flow means nothing either way, could show it).  Error behaviour is
+ *                             hf_batch_run_period's on such a batch: every argument, the chain's included, is checked before the first
+ *                             enqueue; once the early launch is enqueued an error is final.  m_ofcCalcTime then includes the early warps.
  *   hf_batch_scene_read       after hf_batch_sync: the records of one member since the last read, in period order.  *n_records = how many
  *                             there were; min(capacity, *n_records) are copied and leave the ring.  The ring holds 128 periods per member.
  * Additive to ABI version 6: no existing struct or call changed. */
