@@ -1,6 +1,8 @@
-"""Frames for the chain's GPU tests (test_sad_reuse_gpu.py, test_chain_variants_gpu.py, test_chain_saturation_gpu.py): the bench's content
-classes, noise patches inside a static frame, full-range noise, and the saturation kinds (SAT_KINDS) -- pairs whose SADs sit at the top of
-their range, 765 per pixel, the value every width argument of hf_flow.hip is about:
+"""Frames for the chain's GPU tests (test_sad_reuse_gpu.py, test_chain_variants_gpu.py, test_chain_saturation_gpu.py,
+test_chain_deep_rs_gpu.py): the bench's content classes, noise patches inside a static frame, full-range noise, the drift kinds (DRIFT_KINDS:
+one noise field seen through a frame that moves by an odd number of pixels a frame, so that windows at a frame edge settle on offsets that
+point out of the frame at a phase that is neither 0 nor even: drift_frames), and the saturation kinds (SAT_KINDS) -- pairs whose SADs sit
+at the top of their range, 765 per pixel, the value every width argument of hf_flow.hip is about:
   "saturated"   dark, bright, dark, bright, ..: every candidate of every window has the largest SAD there is (zero flow, every window reuses)
   "sat-y"       the same with only the luma plane alternating, the chroma plane mid-grey;   "sat-uv": only the chroma plane, luma mid-grey
   "specks"      a dark frame with bright cells and a bright frame alternate, fresh cells every time.  A cell is 2 x 2 luma pixels (one chroma
@@ -20,7 +22,11 @@ ones, so a plane build that rounds instead of truncating, or lets low bits leak,
 import numpy as np
 
 SAT_KINDS = ("specks", "saturated", "sat-y", "sat-uv")
-KIND_ORDER = ("patches", "chaotic", "noise", "static", "bench", "cut", "pan64") + SAT_KINDS
+# "drift": one field of full-range noise seen through a frame that moves by DRIFT_STEP luma pixels per frame, one kind per direction
+DRIFT_KINDS = ("drift-se", "drift-sw", "drift-ne", "drift-nw")
+DRIFT_STEP = (75, 67)     # (|dx|, |dy|): odd, so no multiple of 2^rs at any rs >= 1, and beyond 2^6: an aligned grid's last column and row lie 2^rs short of the edge
+DRIFT_CELLS = (256, 64, 16, 4)
+KIND_ORDER = ("patches", "chaotic", "noise", "static", "bench", "cut", "pan64") + SAT_KINDS + DRIFT_KINDS
 SPECK_CLEAN = 32          # the clean corner, in grid samples per axis (at most half the grid)
 SPECK_CELL = 2            # luma pixels per fine cell and axis
 SPECK_COARSE_CELL = 4     # fine cells per coarse cell and axis
@@ -104,14 +110,54 @@ def saturation_frame(kind, H, W, hdr, seed, i, in_stride=0, rs=0):
     return f.reshape(-1)
 
 
+def _drift_field(rng, h, w, hdr):
+    """[h][w] codes over the whole range of the element type: cells of DRIFT_CELLS pixels, each scale with its own random level, summed --
+    the difference between the field and its shifted copy grows with the shift up to the largest cell, so the chain's coarse steps find the
+    direction and its fine steps the pixel -- and stretched so that the smallest sum is code 0 and the largest the top code."""
+    f = np.zeros((h, w), dtype=np.float32)
+    for c in DRIFT_CELLS:
+        f += np.repeat(np.repeat(rng.random((-(-h // c), -(-w // c)), dtype=np.float32), c, axis=0), c, axis=1)[:h, :w]
+    f -= f.min()
+    hi = 65535 if hdr else 255
+    return np.minimum(f * ((hi + 1) / f.max()), hi).astype(np.uint16 if hdr else np.uint8)
+
+
+def drift_frames(kind, H, W, hdr, seed, count=3, in_stride=0):
+    """Frame k of a drift kind: the window [k dy, k dy + H) x [k dx, k dx + W) of one field (luma; U and V are fields of their own at half
+    the resolution, moved by the whole chroma samples inside k dx and k dy), (dx, dy) = +-DRIFT_STEP by the kind's direction.  Windows at a
+    frame edge the content drifts across settle on offsets that point out of the frame, by an odd number of pixels.  P010: all 16 bits of
+    a code vary (the stretch leaves the low bits as they fall)."""
+    assert kind in DRIFT_KINDS, kind
+    S = in_stride if in_stride > 0 else W
+    dx = DRIFT_STEP[0] * (1 if kind[-1] == "e" else -1)
+    dy = DRIFT_STEP[1] * (1 if kind[-2] == "s" else -1)
+    px, py = (DRIFT_STEP[0] * (count - 1) + 1) & ~1, (DRIFT_STEP[1] * (count - 1) + 1) & ~1
+    rng = np.random.default_rng(seed)
+    Y = _drift_field(rng, H + 2 * py, W + 2 * px, hdr)
+    U, V = (_drift_field(rng, H // 2 + py, (W + 1) // 2 + px, hdr) for _ in range(2))
+    out = []
+    for k in range(count):
+        y0, x0 = py + k * dy, px + k * dx
+        f = np.zeros((H + H // 2, S), dtype=Y.dtype)
+        f[:H, :W] = Y[y0:y0 + H, x0:x0 + W]
+        cy, cx = y0 >> 1, x0 >> 1
+        f[H:, 0:W:2] = U[cy:cy + H // 2, cx:cx + (W + 1) // 2]
+        f[H:, 1:W:2] = V[cy:cy + H // 2, cx:cx + W // 2]
+        out.append(f.reshape(-1))
+    return out
+
+
 def frames(kind, H, W, hdr, seed, count=3, in_stride=0, rs=0):
     """`count` consecutive frames of content `kind`: "patches", "noise" (every code value: for P010 the low six bits are set too), one of
-    SAT_KINDS (rs: the resolution scalar of the geometry, which places the clean corner and the lattice of "specks") or one of synth.SCENES.
+    SAT_KINDS (rs: the resolution scalar of the geometry, which places the clean corner and the lattice of "specks"), one of DRIFT_KINDS or one
+    of synth.SCENES.
     in_stride: row pitch in elements (0 = W)."""
     from hopperrender_amd import synth
     S = in_stride if in_stride > 0 else W
     if kind in SAT_KINDS:
         return [saturation_frame(kind, H, W, hdr, seed, i, in_stride, rs) for i in range(count)]
+    if kind in DRIFT_KINDS:
+        return drift_frames(kind, H, W, hdr, seed, count, in_stride)
     if kind == "patches":
         a = synth.Scene(H, W, hdr, seed=seed, in_stride=in_stride).frame(0)
         return [a, a] + [patched(a, H, S, hdr, seed + 1 + i) for i in range(count - 2)]

@@ -277,4 +277,91 @@ CASES = [
 
 
 def case(name):
-    return next(c for c in CASES if c.name == name)
+    return next(c for c in CASES + DEEP_CASES if c.name == name)
+
+
+# ------------------------------------------------------------------------------------------------
+# resolution scalars 4, 5 and 6 (tests/test_chain_deep_rs_gpu.py; tests/test_chain_deep_rs_model.py proves what the matrix and its content reach)
+# ------------------------------------------------------------------------------------------------
+# (hdr, H, W, max_res, in_stride) -> (rs, lw, lh): the smallest shapes with H >= 1084, where every offset the chain can reach stays inside
+# one reflection.  The chain's staged Y-row and 8-window forms stop at rs 4 and so does the fast plane kernel: at rs 5 and 6 every tile takes
+# the fallback bodies and the generic kernel builds every plane, 16 or 32 phase-pair rows per luma row.
+DEEP_GEOMETRIES = {
+    (1, 1088, 1536, 68, 0): (4, 96, 68),        # first window 64; the last staged rs; partial tiles at the bottom
+    (0, 1088, 2816, 68, 0): (4, 176, 68),       # first window 128: two large-window levels
+    (0, 1088, 1536, 34, 0): (5, 48, 34),        # first window 32; 1.5 tiles wide, 2 rows below the first tile row
+    (1, 1088, 2816, 34, 0): (5, 88, 34),        # first window 64
+    (1, 1084, 1608, 34, 1616): (5, 51, 34),     # ragged W and H: the ceil grid's last column and row reach beyond the frame
+    (1, 1088, 1536, 17, 0): (6, 24, 17),        # first window 16; the grid is smaller than one tile
+    (0, 2176, 4352, 34, 0): (6, 68, 34),        # large windows at rs 6
+    (0, 1084, 1608, 17, 0): (6, 26, 17),        # ragged at rs 6
+}
+
+DEEP_CASES = [
+    # rs 4, 96 x 68 from P010
+    _c("r4-hdr1536-n1-notab", 1, 1088, 1536, 68, 1, tables=NEVER),
+    _c("r4-hdr1536-n3-tab", 1, 1088, 1536, 68, 3, delta=0, nb=0),
+    _c("r4-hdr1536-n5-default", 1, 1088, 1536, 68, 5, tables=DEFAULT),
+    _c("r4-hdr1536-n13-notab", 1, 1088, 1536, 68, 13, tables=NEVER, delta=10, nb=10),
+    _c("r4-hdr1536-n5-R11", 1, 1088, 1536, 68, 5, R=11),
+    _c("r4-hdr1536-n3-it3-b2", 1, 1088, 1536, 68, 3, it=3, blur=2, tables=NEVER),       # ends at 16: the blur's pixel form at radius 2
+    # rs 4, 176 x 68
+    _c("r4-sdr2816-n1-tab", 0, 1088, 2816, 68, 1, delta=10, nb=10),
+    _c("r4-sdr2816-n3-notab", 0, 1088, 2816, 68, 3, tables=NEVER),
+    _c("r4-sdr2816-n5-notab", 0, 1088, 2816, 68, 5, tables=NEVER),
+    _c("r4-sdr2816-n13-tab", 0, 1088, 2816, 68, 13, delta=0, nb=0),
+    _c("r4-sdr2816-n3-R5", 0, 1088, 2816, 68, 3, R=5, tables=NEVER),
+    # rs 5, 48 x 34
+    _c("r5-sdr1536-n1-tab", 0, 1088, 1536, 34, 1),
+    _c("r5-sdr1536-n3-notab-b2", 0, 1088, 1536, 34, 3, tables=NEVER, blur=2, delta=0, nb=0),
+    _c("r5-sdr1536-n5-tab", 0, 1088, 1536, 34, 5, delta=10, nb=10),
+    _c("r5-sdr1536-n13-tab", 0, 1088, 1536, 34, 13),
+    _c("r5-sdr1536-n3-R5", 0, 1088, 1536, 34, 3, R=5),
+    # rs 5, 88 x 34 from P010
+    _c("r5-hdr2816-n3-tab", 1, 1088, 2816, 34, 3),
+    _c("r5-hdr2816-n5-notab", 1, 1088, 2816, 34, 5, tables=NEVER, delta=0, nb=0),
+    _c("r5-hdr2816-n13-tab-it3", 1, 1088, 2816, 34, 13, it=3),                          # ends at 16
+    _c("r5-hdr2816-n1-notab", 1, 1088, 2816, 34, 1, tables=NEVER, delta=10, nb=10),
+    _c("r5-hdr2816-n5-R11", 1, 1088, 2816, 34, 5, R=11, tables=NEVER),
+    # rs 5, ragged 51 x 34 from P010 rows of 1616
+    _c("r5-hdr1608-n3-notab", 1, 1084, 1608, 34, 3, tables=NEVER, stride=1616),
+    _c("r5-hdr1608-n13-tab", 1, 1084, 1608, 34, 13, stride=1616, delta=0, nb=0),
+    _c("r5-hdr1608-n5-tab", 1, 1084, 1608, 34, 5, stride=1616, delta=10, nb=10),
+    # rs 6, 24 x 17 from P010: no tile lies inside the grid
+    _c("r6-hdr1536-n1-tab", 1, 1088, 1536, 17, 1, delta=0, nb=0),
+    _c("r6-hdr1536-n3-tab-b2", 1, 1088, 1536, 17, 3, blur=2),
+    _c("r6-hdr1536-n5-notab", 1, 1088, 1536, 17, 5, tables=NEVER, delta=10, nb=10),
+    _c("r6-hdr1536-n13-tab", 1, 1088, 1536, 17, 13),
+    _c("r6-hdr1536-n5-tab", 1, 1088, 1536, 17, 5, delta=0, nb=0),
+    # rs 6, 68 x 34 from 2176 x 4352
+    _c("r6-sdr4352-n3-tab", 0, 2176, 4352, 34, 3),
+    _c("r6-sdr4352-n5-notab-it3", 0, 2176, 4352, 34, 5, it=3, tables=NEVER),            # ends at 16
+    _c("r6-sdr4352-n5-R11", 0, 2176, 4352, 34, 5, R=11),
+    # rs 6, ragged 26 x 17
+    _c("r6-sdr1608-n3-notab", 0, 1084, 1608, 17, 3, tables=NEVER, delta=10, nb=10),
+    _c("r6-sdr1608-n5-tab", 0, 1084, 1608, 17, 5),
+    _c("r6-sdr1608-n1-notab", 0, 1084, 1608, 17, 1, tables=NEVER),
+    _c("r6-sdr1608-n3-R5", 0, 1084, 1608, 17, 3, R=5, tables=NEVER),
+]
+# flags beside the table mode (tests/test_chain_deep_rs_gpu.py): a batch with large windows without the lazy argmin, a lone context without its graph
+DEEP_NO_LAZY, DEEP_NO_GRAPH = "r5-hdr2816-n5-notab", "r5-hdr2816-n1-notab"
+
+# Content of the members (tests/chain_content.py): the four drift directions and full-range noise first, so that every batch of five has
+# them -- windows at each frame edge then settle on offsets that point out of the frame -- then the other kinds on which the oracle samples
+# nothing beyond the single reflection at these shapes.
+DEEP_KINDS = ["drift-se", "drift-nw", "noise", "drift-sw", "drift-ne", "chaotic", "patches", "pan64", "static"]
+
+
+def deep_member_kinds(c):
+    """Content of member i of a deep case.  A lone context runs the first four kinds one after the other; three members start where the
+    case's place in DEEP_CASES says, so that every kind runs at that size too (tests/test_chain_deep_rs_model.py: every geometry runs the drifts and
+    noise, every resolution scalar every kind)."""
+    if c.n == 1:
+        return DEEP_KINDS[:4]
+    pool = DEEP_KINDS[:5] if c.H > 1088 else DEEP_KINDS       # (the 2176 x 4352 frames: the kinds that take no seconds to draw)
+    s = [x.name for x in DEEP_CASES].index(c.name) * 3 if c.n == 3 else 0
+    return [pool[(s + i) % len(pool)] for i in range(c.n)]
+
+
+def deep_geom_key(c):
+    return (c.hdr, c.H, c.W, c.max_res, c.in_stride)
