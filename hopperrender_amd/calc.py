@@ -167,6 +167,36 @@ class OpticalFlowCalc:
     def downloadFrameDevice(self, dev_ptr):
         capi.check(self._lib.hf_download_frame_device(self._ctx, C.c_void_p(dev_ptr)), self._ctx)
 
+    # ---- frame error sums on the device (hf_frame_error*) ----
+    @staticmethod
+    def _frame_error_dict(e):
+        """struct hf_frame_error as {'Y': {...}, 'U': {...}, 'V': {...}} of plain ints: sse, sad, max_abs, n_differ, count"""
+        return {p: {k: int(getattr(e, k)[i]) for k in ("sse", "sad", "max_abs", "n_differ", "count")} for i, p in enumerate("YUV")}
+
+    def frameErrorEnqueue(self, a_ptrs, b_ptrs, first_slot=0, stride_a=0, stride_b=0, planar=False):
+        """hf_frame_error_enqueue: compare device frames a_ptrs[i] and b_ptrs[i] into result slot first_slot + i, behind everything this
+        context has enqueued; only enqueues.  Strides in elements, 0 = the frame width."""
+        n = len(a_ptrs)
+        if len(b_ptrs) != n:
+            raise ValueError("frameErrorEnqueue: as many b frames as a frames")
+        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
+        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
+        capi.check(self._lib.hf_frame_error_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
+                                                    1 if planar else 0, int(first_slot)), self._ctx)
+
+    def frameErrorRead(self, first_slot, n):
+        """hf_frame_error_read: wait for this context's work and return result slots [first_slot, first_slot + n) as dicts."""
+        out = (capi.HfFrameError * max(int(n), 1))()
+        capi.check(self._lib.hf_frame_error_read(self._ctx, int(first_slot), int(n), out), self._ctx)
+        return [self._frame_error_dict(e) for e in out[:n]]
+
+    def frameError(self, a_ptr, b_ptr, stride_a=0, stride_b=0, planar=False):
+        """hf_frame_error: one pair, blocking."""
+        e = capi.HfFrameError()
+        capi.check(self._lib.hf_frame_error(self._ctx, C.c_void_p(a_ptr or 0), C.c_void_p(b_ptr or 0), int(stride_a) or self.m_frameWidth,
+                                            int(stride_b) or self.m_frameWidth, 1 if planar else 0, C.byref(e)), self._ctx)
+        return self._frame_error_dict(e)
+
     def setOutputBuffer(self, dev_ptr):
         capi.check(self._lib.hf_set_output_buffer(self._ctx, C.c_void_p(dev_ptr or 0)), self._ctx)
 

@@ -26,6 +26,8 @@ HF_FLAG_BATCH_PLANAR_OUT = 0x40000   # on a batch's leader: the batch's caller-o
 HF_FLAG_BATCH_AUTO_DEFERRED = 0x80000  # on a batch's leader: runPeriodAuto accepts a batch that defers its phase planes and keeps the deferred order
 HF_MAX_PERIOD_OUTPUTS = 6
 HF_MAX_PERIOD_OUTPUTS_WIDE = 24   # the *_wide period calls: 23.976 fps -> 480 Hz is 21 outputs per source period
+HF_MAX_ERROR_PAIRS = 192          # frame pairs of one hf_frame_error_enqueue launch
+HF_ERROR_SLOTS = 256              # result slots of a context
 
 (HF_OK, HF_ERR_INVALID_ARGUMENT, HF_ERR_NO_DEVICE, HF_ERR_OUT_OF_MEMORY, HF_ERR_HIP, HF_ERR_STATE) = (0, -1, -2, -3, -4, -5)
 
@@ -82,6 +84,12 @@ class HfTimelineRecord(C.Structure):
 class HfSceneRecord(C.Structure):
     _fields_ = [("frame_count", C.c_uint32), ("total_delta", C.c_uint32), ("kind", C.c_int32), ("average", C.c_int32), ("d1", C.c_int32),
                 ("d2", C.c_int32)]
+
+
+class HfFrameError(C.Structure):
+    """struct hf_frame_error: the integer error sums of one frame pair, index 0 Y, 1 U, 2 V"""
+    _fields_ = [("sse", C.c_uint64 * 3), ("sad", C.c_uint64 * 3), ("n_differ", C.c_uint64 * 3), ("count", C.c_uint64 * 3),
+                ("max_abs", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
 class HfDebugCounters(C.Structure):
@@ -156,6 +164,9 @@ SIGNATURES = {
     "hf_debug_counters_enable": (_i, [_vp, _i]),
     "hf_debug_counters_read": (_i, [_vp, C.POINTER(HfDebugCounters), _i]),
     "hf_batch_last_error": (C.c_char_p, [_vp]),
+    "hf_frame_error_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i]),
+    "hf_frame_error_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameError)]),
+    "hf_frame_error": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(HfFrameError)]),
     "hf_download_frame_device": (_i, [_vp, _vp]),
     "hf_set_output_buffer": (_i, [_vp, _vp]),
     "hf_sync": (_i, [_vp]),

@@ -360,6 +360,7 @@ void hf_destroy(hf_ctx* c) {
     if (c->still_count) hipFree(c->still_count);
     if (c->counters) hipFree(c->counters);
     if (c->d_probe) hipFree(c->d_probe);
+    if (c->error_slots) hipFree(c->error_slots);
     if (c->h_total_delta) hipHostFree(c->h_total_delta);
     for (auto& sp : c->spans) { hipEventDestroy(sp.b); hipEventDestroy(sp.e); }
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
@@ -559,8 +560,9 @@ int hf_debug_bounds_violations(hf_ctx* c, uint32_t* count, uint32_t first[4], in
     if (hipDeviceSynchronize() != hipSuccess) return fail(c, HF_ERR_HIP, "hf_debug_bounds_violations: hipDeviceSynchronize failed");
     unsigned rec[5] = {0, 0, 0, 0, 0};
     const bool a = hf::dbg_bounds_read_kernels(rec, reset != 0), b = hf::dbg_bounds_read_flow(rec, reset != 0),
-               p = hf::dbg_bounds_read_planar(rec, reset != 0), s = hf::dbg_bounds_read_scene(rec, reset != 0);
-    if (!a || !b || !p || !s) return fail(c, HF_ERR_STATE, "hf_debug_bounds_violations: this library was built without -DHF_DEBUG_BOUNDS (python -m hopperrender_amd.build --debug-bounds)");
+               p = hf::dbg_bounds_read_planar(rec, reset != 0), s = hf::dbg_bounds_read_scene(rec, reset != 0),
+               m = hf::dbg_bounds_read_metrics(rec, reset != 0);
+    if (!a || !b || !p || !s || !m) return fail(c, HF_ERR_STATE, "hf_debug_bounds_violations: this library was built without -DHF_DEBUG_BOUNDS (python -m hopperrender_amd.build --debug-bounds)");
     *count = rec[0];
     if (first) for (int i = 0; i < 4; i++) first[i] = rec[1 + i];
     return HF_OK;

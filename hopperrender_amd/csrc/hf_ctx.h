@@ -11,6 +11,7 @@
 //                    fused or member-by-member warps, predicated copy, planar conversion): hf_interpolate_period is its n = 1 case
 //   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
 //                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
+//   hf_metrics.hip   frame error sums on the device (hf_frame_error*): kernel, launcher and the three calls
 //   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async: the H2D, then update_frames;
 //                    hf_download_frame_async, hf_wait_*)
 //
@@ -127,6 +128,7 @@ struct hf_ctx {
     uint32_t* d_total_delta = nullptr;                 // device view of h_total_delta (mapped pinned memory)
     uint32_t* h_total_delta = nullptr;                 // pinned host slot the chain writes m_totalFrameDelta into
     float* d_probe = nullptr;
+    hf::FrameErrorSlot* error_slots = nullptr;         // hf_frame_error* (hf_metrics.hip): HF_ERROR_SLOTS + 1 result slots, allocated on first use
 
     // asynchronous host I/O (hf_update_frame_async / hf_download_frame_async): side streams, created lazily
     static constexpr int kOutRing = 3;

@@ -190,6 +190,17 @@ constexpr int kMaxPlanarOutPairs = kMaxFlowBatch * kMaxWarpOutputs;
 void launch_planar_in_batch(int hdr, int H, int stride, int n, const PlanarPair* pairs, hipStream_t stream);
 void launch_planar_out_batch(int hdr, int H, int stride, int n, const PlanarPair* pairs, hipStream_t stream);
 bool dbg_bounds_read_planar(unsigned out[5], bool reset);
+// Frame error sums (hf_metrics.hip; hf_frame_error*): pair i of n <= kMaxErrorPairs compares frames a[i] and b[i] -- H rows of W elements,
+// strides in elements per side, both NV12 / P010 or both planar -- into slots[i], which the caller zeroed on the same stream.  The layout
+// of hf_frame_error (include/hopperflow.h).  false: nothing launched (n out of range, a frame beyond 2^32 work items).
+struct FrameErrorSlot {
+    uint64_t sse[3], sad[3], n_differ[3], count[3];   // index 0 Y, 1 U, 2 V
+    uint32_t max_abs[3], reserved;
+};
+constexpr int kMaxErrorPairs = 192;
+bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
+                         FrameErrorSlot* slots, hipStream_t stream);
+bool dbg_bounds_read_metrics(unsigned out[5], bool reset);
 // Scene-cut copy periods of a batch, decided on the device (hf_scene.hip; hf_batch_run_period_auto).  One record per member and period:
 // the layout of hf_scene_record (include/hopperflow.h).
 struct SceneRecord {

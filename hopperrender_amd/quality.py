@@ -1,0 +1,307 @@
+"""Leave-one-out interpolation quality of a clip, measured on the device.
+
+    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--report out.json]
+    python -m hopperrender_amd.quality clip.nv12 --width 1920 --height 1080 [--hdr | --pix-fmt yuv420p10le] ...
+
+Every second frame of the clip is withheld: the sources S_j = frames[2 j] go through one asynchronous context exactly as a filter would
+feed them (hf_interpolate_period on device frames, ONE output at t = 0.5, blended mode), and what comes out for the pair (S_p, S_p+1) is
+compared with the withheld frame T_p = frames[2 p + 1] between them.  That is the only question the six knobs that change the picture
+(search radius, delta and neighbour scalar, blur radius, iterations, calculation resolution) can be asked without a reference to copy.
+
+Which period shows which pair follows the filter's gating (protocol.FilterReplay.deliver, HopperRender.cpp:955,1179): a flow is only
+calculated once three frames have arrived, and the period of source S_j shows the pair (S_j-2, S_j-1) with the flow calculated ONE period
+earlier.  So pair 0 is shown before any flow exists -- it is listed as warm-up and not evaluated -- and the last source is submitted once
+more so that the last pair is reached (schedule()).
+
+Outputs carry the context's levels (HDR: the x 65535 / 65280 stretch of the default 0 .. 255 levels), so the truth of a pair is the
+withheld frame through copyFrame's arithmetic at the same levels, from a second context; the baseline "frame repeat" is copyFrame of the
+pair's first source against the same truth.  The comparison itself is the device's integer frame error (hf_frame_error_enqueue:
+sum of squared / absolute differences, largest difference, differing elements per plane, padding excluded), enqueued straight behind
+each period with no host sync and read once per chunk of 128 pairs -- once at the end for any ordinary clip.
+
+The report is a plain dict (json.dump-able): per evaluated pair and plane the integer sums and psnr = 10 log10(peak^2 count / sse)
+(peak 255 or 65535; None where sse == 0) for the interpolation and for the repeat baseline, clip aggregates (PSNR of the summed sse, the
+worst pair), the settings, and -- on request -- what the filter's scene-change detection would have made of each period.
+"""
+import argparse
+import itertools
+import json
+import math
+import sys
+
+PLANES = ("Y", "U", "V")
+SUMS = ("sse", "sad", "max_abs", "n_differ", "count")
+SETTINGS = {"search_radius": 16, "delta_scalar": 8, "neighbor_scalar": 6, "blur_radius": 0, "iterations": 0, "max_calc_res": 270}
+PAIRS_PER_READ = 128   # two result slots per pair (interpolation, repeat) out of HF_ERROR_SLOTS
+
+
+def psnr(sse, count, peak):
+    """10 log10(peak^2 count / sse) in dB; None where the frames are equal (or nothing was compared)."""
+    if sse == 0 or count == 0:
+        return None
+    return 10.0 * math.log10(float(peak) * float(peak) * float(count) / float(sse))
+
+
+def schedule(n_frames):
+    """The periods of a leave-one-out run over n_frames frames: one dict per call the evaluator makes, in order --
+         period        j
+         source_frame  index of the frame submitted (frames[2 j]; the last source once more at the end)
+         flow          a flow is calculated (the filter's gating: from the third frame on)
+         pair          the pair (S_pair, S_pair+1) the period's output shows, None before there is one
+         truth_frame   index of the withheld frame between them
+         evaluated     False for pair 0, which is shown before any flow has been calculated (warm-up)"""
+    n_src = (n_frames + 1) // 2
+    if n_src < 3:
+        raise ValueError(f"leave-one-out needs at least 5 frames (3 sources), got {n_frames}")
+    out = []
+    for j in range(n_src + 1):
+        pair = j - 2 if j >= 2 else None
+        out.append({"period": j, "source_frame": 2 * min(j, n_src - 1), "flow": j >= 2, "pair": pair,
+                    "truth_frame": None if pair is None else 2 * pair + 1, "evaluated": pair is not None and pair >= 1})
+    return out
+
+
+class _Device:
+    """What evaluate() needs of the library: calculators and device buffers (a test hands in a recording fake)."""
+
+    def __init__(self, device_index=0):
+        self.device_index = device_index
+
+    def calc(self, hdr, H, W, black, white, settings):
+        from . import capi
+        from .calc import OpticalFlowCalcHDR, OpticalFlowCalcSDR
+        return (OpticalFlowCalcHDR if hdr else OpticalFlowCalcSDR)(
+            H, W, 0, 0, settings["delta_scalar"], settings["neighbor_scalar"], black, white, settings["max_calc_res"],
+            device_index=self.device_index, iterations=settings["iterations"], blur_radius=settings["blur_radius"],
+            search_radius=settings["search_radius"], flags=capi.HF_FLAG_ASYNC)
+
+    def buffer(self, nbytes):
+        from .calc import DeviceBuffer
+        return DeviceBuffer(nbytes, self.device_index)
+
+    def scene_filter(self, source_frame_time, threshold):
+        from .protocol import NativeFilter
+        return NativeFilter(source_frame_time, scene_change_threshold=threshold)
+
+
+def _with_psnr(err, peak):
+    return {p: dict({k: int(err[p][k]) for k in SUMS}, psnr=psnr(err[p]["sse"], err[p]["count"], peak)) for p in PLANES}
+
+
+def _aggregate(rows, key, peak):
+    out = {}
+    for p in PLANES:
+        sse, cnt = sum(r[key][p]["sse"] for r in rows), sum(r[key][p]["count"] for r in rows)
+        out[p] = {"sse": sse, "sad": sum(r[key][p]["sad"] for r in rows), "max_abs": max(r[key][p]["max_abs"] for r in rows),
+                  "n_differ": sum(r[key][p]["n_differ"] for r in rows), "count": cnt, "psnr": psnr(sse, cnt, peak)}
+    return out
+
+
+def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
+             device_index=0, device=None, **settings):
+    """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
+    settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
+    library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
+    scene-change detection would have taken per period (costs one wait per period; the outputs evaluated are always the warps)."""
+    unknown = set(settings) - set(SETTINGS)
+    if unknown:
+        raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
+    st = dict(SETTINGS, **{k: int(v) for k, v in settings.items()})
+    dev = device or _Device(device_index)
+    sched = schedule(len(frames))
+    peak = 65535 if hdr else 255
+    main = dev.calc(hdr, H, W, black, white, st)
+    aux = dev.calc(hdr, H, W, black, white, st)     # copyFrame at the same levels: the truths and the repeat baseline
+    filt = dev.scene_filter(source_frame_time, scene_threshold) if detect_scene_cuts else None
+    frame_bytes, out_bytes = int(main.input_frame_bytes), int(main.output_frame_bytes)
+    free_in, free_out, rows, cuts = [], [], [], []
+    take = lambda pool, nbytes: pool.pop() if pool else dev.buffer(nbytes)
+    src = {}    # period -> device frame of its source; the last three outlive a chunk (the context's ring still references them)
+    try:
+        todo = list(sched)
+        while todo:
+            # a chunk: the periods up to PAIRS_PER_READ evaluated pairs
+            chunk, n_eval = [], 0
+            while todo and n_eval < PAIRS_PER_READ:
+                chunk.append(todo.pop(0))
+                n_eval += chunk[-1]["evaluated"]
+            used_in, used_out = [], []
+            # sources, truths and baselines of the chunk first; the second context is waited for ONCE, before the clip context starts
+            for s in chunk:
+                src[s["period"]] = take(free_in, frame_bytes)
+                src[s["period"]].upload(frames[s["source_frame"]])
+            jobs = {}
+            for s in (s for s in chunk if s["evaluated"]):
+                t_raw = take(free_in, frame_bytes)
+                t_raw.upload(frames[s["truth_frame"]])
+                used_in.append(t_raw)
+                truth, repeat, out = take(free_out, out_bytes), take(free_out, out_bytes), take(free_out, out_bytes)
+                used_out += [truth, repeat, out]
+                for raw, dst in ((t_raw, truth), (src[s["period"] - 2], repeat)):   # the pair's first source was submitted two periods earlier
+                    aux.m_frameCount = 0            # copyFrame then shows the frame just submitted (opticalFlowCalcSDR.cpp:173)
+                    aux.setOutputBuffer(dst.ptr)
+                    aux.updateFrameDevice(raw.ptr)
+                    aux.copyFrame()
+                jobs[s["period"]] = (truth, repeat, out)
+            aux.sync()
+            # the clip: periods and comparisons back to back, nothing waits on the host (unless the caller asked for the cut decisions)
+            scratch = take(free_out, out_bytes)     # where the warm-up pair's output goes
+            used_out.append(scratch)
+            slot = 0
+            for s in chunk:
+                b = src[s["period"]]
+                if filt is not None:
+                    filt.begin_source_frame()
+                if not s["flow"]:
+                    main.updateFrameDeviceRef(b.ptr)
+                    continue
+                truth, repeat, out = jobs.get(s["period"], (None, None, scratch))
+                main.interpolatePeriod(b.ptr, [0.5], [out.ptr], 2)
+                if s["evaluated"]:
+                    main.frameErrorEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
+                    slot += 2
+                if filt is not None:
+                    main.waitFlow()
+                    fc, delta = int(main.m_frameCount), int(main.m_totalFrameDelta)
+                    filt.push(fc, delta)
+                    cuts.append({"period": s["period"], "pair": s["pair"], "total_frame_delta": delta,
+                                 "kind": "copy" if filt.detect(fc) else "warp"})
+            got = main.frameErrorRead(0, slot) if slot else []
+            for i, s in enumerate(s for s in chunk if s["evaluated"]):
+                row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
+                       "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
+                a, r = row["interpolated"]["Y"]["psnr"], row["repeat"]["Y"]["psnr"]
+                row["gain_db_y"] = None if a is None or r is None else a - r
+                rows.append(row)
+            # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
+            last = chunk[-1]["period"]
+            free_in += used_in + [src.pop(j) for j in sorted(src) if j <= last - 3]
+            free_out += used_out
+    finally:
+        main.close()
+        aux.close()
+        if filt is not None:
+            filt.close()
+        for b in free_in + free_out + list(src.values()):
+            b.free()
+    worst = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["psnr"] is None else r["interpolated"]["Y"]["psnr"])
+    clip = {"interpolated": _aggregate(rows, "interpolated", peak), "repeat": _aggregate(rows, "repeat", peak),
+            "worst_pair": {"pair": worst["pair"], "psnr_y": worst["interpolated"]["Y"]["psnr"]}}
+    a, r = clip["interpolated"]["Y"]["psnr"], clip["repeat"]["Y"]["psnr"]
+    clip["gain_db_y"] = None if a is None or r is None else a - r
+    return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
+            "settings": dict(st, black_level=float(black), white_level=float(white)),
+            "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
+            "pairs": rows, "clip": clip, "scene_cuts": cuts if detect_scene_cuts else None}
+
+
+# ---- command line ----
+SWEEP_KEYS = {"radius": "search_radius", "delta": "delta_scalar", "neighbor": "neighbor_scalar", "blur": "blur_radius",
+              "iterations": "iterations", "max-calc-res": "max_calc_res", "max_calc_res": "max_calc_res"}
+SWEEP_KEYS.update({v: v for v in list(SWEEP_KEYS.values())})
+
+
+class _ClipFrames:
+    """The frames of a cli._Clip as a sequence of NV12 / P010 host frames (planar raw files re-laid on the host: this is measurement)."""
+
+    def __init__(self, clip, planar_raw, limit=0):
+        self.clip, self.planar_raw = clip, planar_raw
+        self.n = min(clip.n_frames, limit) if limit else clip.n_frames
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, k):
+        import numpy as np
+        c = self.clip
+        out = np.empty(c.n_el, dtype=c.dt)
+        if c.y4m or not self.planar_raw:
+            c.read_into(k, out)
+            return out
+        from .y4m import planar_to_semiplanar
+        c.read_raw_into(k, out)
+        H, W = c.height, c.width
+        return planar_to_semiplanar(out[:H * W].reshape(H, W), out[H * W:H * W * 5 // 4].reshape(H // 2, W // 2),
+                                    out[H * W * 5 // 4:].reshape(H // 2, W // 2), c.hdr).reshape(-1)
+
+
+def parse_sweeps(specs):
+    """['radius=5,16', 'blur=4,32'] -> [{'search_radius': 5, 'blur_radius': 4}, ...]: the cartesian product, in order."""
+    keys, values = [], []
+    for spec in specs or []:
+        k, _, v = spec.partition("=")
+        if k.strip() not in SWEEP_KEYS or not v:
+            raise ValueError(f"--sweep {spec!r}: KEY=v1,v2,... with KEY one of {sorted(set(SWEEP_KEYS))}")
+        keys.append(SWEEP_KEYS[k.strip()])
+        values.append([int(x) for x in v.split(",")])
+    return [dict(zip(keys, combo)) for combo in itertools.product(*values)]
+
+
+def parse_args(argv=None):
+    from .cli import PIX_FMTS
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("input")
+    ap.add_argument("--width", type=int); ap.add_argument("--height", type=int)
+    ap.add_argument("--hdr", action="store_true")
+    ap.add_argument("--pix-fmt", choices=sorted(PIX_FMTS), default=None,
+                    help="layout of a raw input: nv12 / p010 (default, by --hdr) or planar yuv420p / yuv420p10le (10-bit formats imply --hdr)")
+    ap.add_argument("--radius", type=int, default=SETTINGS["search_radius"]); ap.add_argument("--delta", type=int, default=SETTINGS["delta_scalar"])
+    ap.add_argument("--neighbor", type=int, default=SETTINGS["neighbor_scalar"]); ap.add_argument("--blur", type=int, default=SETTINGS["blur_radius"], help="blur radius (0: the reference's 4)")
+    ap.add_argument("--iterations", type=int, default=SETTINGS["iterations"], help="refinement iterations (0: auto)")
+    ap.add_argument("--max-calc-res", type=int, default=SETTINGS["max_calc_res"])
+    ap.add_argument("--black", type=float, default=0.0); ap.add_argument("--white", type=float, default=255.0)
+    ap.add_argument("--source-fps", type=float, default=None, help="only for --detect-cuts: default 23.976, or the .y4m header's rate")
+    ap.add_argument("--detect-cuts", action="store_true", help="also report the filter's warp / copy decision per period")
+    ap.add_argument("--scene-threshold", type=int, default=200)
+    ap.add_argument("--max-frames", type=int, default=0, help="evaluate only the first N frames")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--sweep", action="append", metavar="KEY=v1,v2,...",
+                    help="evaluate every value of a knob (radius, delta, neighbor, blur, iterations, max-calc-res); repeatable: the cartesian product")
+    ap.add_argument("--report", default=None, help="write the reports as JSON")
+    a = ap.parse_args(argv)
+    if a.pix_fmt is None:
+        a.pix_fmt = "p010" if a.hdr else "nv12"
+    elif PIX_FMTS[a.pix_fmt][0]:
+        a.hdr = True
+    elif a.hdr:
+        ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
+    try:
+        a.sweeps = parse_sweeps(a.sweep)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def _db(x):
+    return "  equal" if x is None else f"{x:7.3f}"
+
+
+def main(argv=None, device=None):
+    """Evaluates the clip once per setting of the sweep (once without --sweep), prints one line per setting; returns the reports."""
+    from .cli import PIX_FMTS, _Clip
+    a = parse_args(argv)
+    clip = _Clip(a.input, a.width, a.height, a.hdr, a.source_fps)
+    frames = _ClipFrames(clip, PIX_FMTS[a.pix_fmt][1], a.max_frames)
+    base = {"search_radius": a.radius, "delta_scalar": a.delta, "neighbor_scalar": a.neighbor, "blur_radius": a.blur,
+            "iterations": a.iterations, "max_calc_res": a.max_calc_res}
+    reports = []
+    for sweep in a.sweeps:
+        st = dict(base, **sweep)
+        rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
+                       scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
+                       device=device, **st)
+        reports.append(rep)
+        c = rep["clip"]
+        knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
+        print(f"{knobs}  pairs {len(rep['pairs'])}  PSNR Y/U/V {_db(c['interpolated']['Y']['psnr'])} {_db(c['interpolated']['U']['psnr'])} "
+              f"{_db(c['interpolated']['V']['psnr'])} dB  repeat Y {_db(c['repeat']['Y']['psnr'])} dB  gain {_db(c['gain_db_y'])} dB  "
+              f"worst pair {c['worst_pair']['pair']} ({_db(c['worst_pair']['psnr_y'])} dB)")
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump({"input": a.input, "reports": reports}, f, indent=1)
+    return reports
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

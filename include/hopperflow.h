@@ -360,6 +360,39 @@ int hf_batch_sync(hf_batch* batch);   /* hf_sync() of every member */
 int hf_batch_size(const hf_batch* batch);
 const char* hf_batch_last_error(const hf_batch* batch);   /* batch == NULL: error of the last failed hf_batch_create (per thread) */
 
+/* ---- Frame error sums on the device: how far two frames are apart, without reading them back ----
+ * What a leave-one-out quality evaluation needs (withhold every second frame, interpolate it, compare: hopperrender_amd/quality.py), and
+ * a cheap "how many elements differ, and by how much" for tests.  One launch compares up to HF_MAX_ERROR_PAIRS pairs (a[i], b[i]) of
+ * frames of ctx's geometry (frame_width, frame_height, 8 or 16 bit); each side has its own stride in elements (>= frame_width), and
+ * both frames of a pair are NV12 / P010 (planar = 0) or both planar as defined at HF_FLAG_PLANAR_IN (planar = 1: even strides).  Per
+ * plane -- index 0 Y, 1 U, 2 V, interleaved UV split -- over the elements of columns [0, frame_width) (chroma: [0, frame_width / 2)):
+ *     sse = sum (a - b)^2    sad = sum |a - b|    max_abs = max |a - b|    n_differ = #(a != b)    count = elements compared
+ * Values are compared as stored (raw 16-bit P010 words; LSB-aligned words in planar HDR frames).  Padding columns [frame_width, stride)
+ * are never read, so an output's unspecified padding cannot reach a sum.  Integer sums: the results are exact and reproducible.
+ *   hf_frame_error_enqueue  only enqueues: zeroes result slots [first_slot, first_slot + n) of ctx and compares pair i into slot
+ *                           first_slot + i.  Ordered like hf_download_frame_device: behind every warp, copy and update ctx has enqueued
+ *                           (the warp stream of an HF_FLAG_DUAL_STREAM context included); a batch member enqueues onto its batch's stream.
+ *                           So a driver calls it straight after hf_interpolate_period / hf_batch_run_period* with no sync, and reads
+ *                           the slots at the end of the clip.  The frames must stay as they are until the comparison has run.
+ *   hf_frame_error_read     waits for ctx's work (hf_sync) and copies n slots out.
+ *   hf_frame_error          one pair, blocking; uses a slot of its own outside [0, HF_ERROR_SLOTS).
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued: NULL tables or entries, n outside [1, HF_MAX_ERROR_PAIRS], a slot range outside
+ * [0, HF_ERROR_SLOTS), a stride below frame_width, an odd stride with planar = 1.  The slots (28 KB) are allocated on first use and
+ * freed with the context.  Additive to ABI version 6. */
+#define HF_MAX_ERROR_PAIRS 192
+#define HF_ERROR_SLOTS 256
+struct hf_frame_error {   /* index 0 Y, 1 U, 2 V.  A struct tag only, no typedef: the one-pair call below carries the same name, and in C a
+                           * typedef name and a function share one name space (write `struct hf_frame_error`, in C++ too) */
+    uint64_t sse[3], sad[3], n_differ[3], count[3];
+    uint32_t max_abs[3];
+    uint32_t reserved;
+};
+int hf_frame_error_enqueue(hf_ctx* ctx, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b,
+                           int planar, int first_slot);
+int hf_frame_error_read(hf_ctx* ctx, int first_slot, int n, struct hf_frame_error* out);
+int hf_frame_error(hf_ctx* ctx, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar,
+                   struct hf_frame_error* out);
+
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
 /* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
