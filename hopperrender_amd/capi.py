@@ -97,6 +97,12 @@ class HfDebugCounters(C.Structure):
                 ("level_reused", (C.c_uint32 * 2) * 16), ("level_window_size", C.c_int32 * 16)]
 
 
+class HfLiveResources(C.Structure):
+    """struct hf_live_resources: what the library holds for itself in this process, per kind (hf_debug_live_resources)"""
+    _fields_ = [("device_buffers", C.c_int64), ("pinned_buffers", C.c_int64), ("streams", C.c_int64), ("events", C.c_int64),
+                ("graph_execs", C.c_int64)]
+
+
 class HfProfile(C.Structure):
     _fields_ = [("warp_launches", C.c_uint64), ("warp_ms", C.c_double), ("copy_launches", C.c_uint64),
                 ("copy_ms", C.c_double), ("flow_chains", C.c_uint64), ("flow_ms", C.c_double), ("warp_frames", C.c_uint64)]
@@ -163,6 +169,7 @@ SIGNATURES = {
     "hf_batch_timeline_dropped": (C.c_uint64, [_vp]),
     "hf_debug_counters_enable": (_i, [_vp, _i]),
     "hf_debug_counters_read": (_i, [_vp, C.POINTER(HfDebugCounters), _i]),
+    "hf_debug_live_resources": (_i, [C.POINTER(HfLiveResources)]),
     "hf_batch_last_error": (C.c_char_p, [_vp]),
     "hf_frame_error_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i]),
     "hf_frame_error_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameError)]),
@@ -253,6 +260,13 @@ def _debug_bounds_exit_check():
         sys.stderr.write(f"[HopperRender] HF_DEBUG_BOUNDS: out-of-range gather indices recorded in process {os.getpid()}: {bad} (device: (count, [site, block, thread, line]))\n")
         sys.stderr.flush()
         os._exit(97)
+
+
+def live_resources():
+    """hf_debug_live_resources as a dict: the library's own device buffers, pinned buffers, streams, events and graph executables alive now"""
+    r = HfLiveResources()
+    check(load().hf_debug_live_resources(C.byref(r)))
+    return {name: getattr(r, name) for name, _ in HfLiveResources._fields_}
 
 
 def lib_path():

@@ -137,7 +137,7 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: hipSetDevice failed");
     for (int i = 0; i < n; i++)   // before any member is touched: a failure leaves every context as it was
         if (int rc = sync_ctx(members[i])) return batch_fail(nullptr, rc, "hf_batch_create: member sync failed: " + members[i]->err);
-    hf_batch* b = new (std::nothrow) hf_batch();
+    std::unique_ptr<hf_batch> b(new (std::nothrow) hf_batch());   // (its streams: built here, before any member is touched; all or nothing)
     if (!b) return batch_fail(nullptr, HF_ERR_OUT_OF_MEMORY, "hf_batch_create: host allocation failed");
     // A stream of the batch's own, of the HIGHEST priority.  Not for the priority: the runtime keeps one pool of hardware queues
     // per priority level and hands a new stream the queue of its pool with the fewest users.  The members' streams (and
@@ -150,13 +150,9 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     {
         int prio_low = 0, prio_high = 0;
         const bool want_high = !(l->cfg.flags & HF_FLAG_BATCH_NORMAL_PRIORITY) && hipDeviceGetStreamPriorityRange(&prio_low, &prio_high) == hipSuccess;
-        if (!want_high || hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, prio_high) != hipSuccess) {
+        if (!want_high || create_stream(b->stream, &prio_high) != hipSuccess) {
             (void)hipGetLastError();
-            b->stream = nullptr;
-            if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
-                delete b;
-                return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: cannot create the batch stream");
-            }
+            if (create_stream(b->stream) != hipSuccess) return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: cannot create the batch stream");
         }
     }
     if (l->dual()) {
@@ -164,14 +160,9 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
         // runs only a handful of hardware queues side by side (DESIGN.md "Hardware queues")
         const int nws = n < 3 ? n : 3;
         for (int i = 0; i < nws; i++) {
-            hipStream_t ws = nullptr;
-            if (hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) != hipSuccess) {
-                for (hipStream_t x : b->warp_streams) hipStreamDestroy(x);
-                hipStreamDestroy(b->stream);
-                delete b;
-                return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: cannot create a warp stream");
-            }
-            b->warp_streams.push_back(ws);
+            Stream ws;
+            if (create_stream(ws) != hipSuccess) return batch_fail(nullptr, HF_ERR_HIP, "hf_batch_create: cannot create a warp stream");
+            b->warp_streams.push_back(std::move(ws));
         }
     }
     for (int i = 0; i < n; i++) {
@@ -181,9 +172,9 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
         b->own_warp_streams.push_back(m->warp_stream);
         // one stream for the whole batch: the members' prep / warp launches and the batched chain stay in program order
         m->graphs.clear();   // captured on the member's own stream
-        m->stream = b->stream;
-        m->warp_stream = m->dual() ? b->warp_streams[(size_t)i % b->warp_streams.size()] : b->stream;
-        m->batch = b;
+        m->stream = b->stream.get();
+        m->warp_stream = m->dual() ? b->warp_streams[(size_t)i % b->warp_streams.size()].get() : b->stream.get();
+        m->batch = b.get();
     }
     // Deferred phase planes: where the batched period warp is the workgroup-staged kernel it can build the full plane of the frame
     // it reads anyway (plane-building workgroups of warp_wg_kernel, hf_kernels.hip); hf_batch_run_period then only samples the grid
@@ -194,7 +185,7 @@ int hf_batch_create(hf_ctx* const* members, int n, hf_batch** out) {
     b->auto_deferred = b->defer_planes && (l->cfg.flags & HF_FLAG_BATCH_AUTO_DEFERRED) != 0;
     b->planar_in = planar_in;
     b->planar_out = planar_out;
-    *out = b;
+    *out = b.release();
     return HF_OK;
 }
 
@@ -202,28 +193,19 @@ void hf_batch_destroy(hf_batch* b) {
     if (!b) return;
     if (!b->members.empty()) hipSetDevice(b->members[0]->device);
     for (hf_ctx* m : b->members) leave_warp_stream(m);   // the batch stream waits for every member's last warps
-    if (b->stream) hipStreamSynchronize(b->stream);
-    for (hipStream_t ws : b->warp_streams) hipStreamSynchronize(ws);
+    if (b->stream) hipStreamSynchronize(b->stream.get());
+    for (const Stream& ws : b->warp_streams) hipStreamSynchronize(ws.get());
+    // Nothing of the batch is in flight from here on: the order in which its owners (streams, timeline events, scene state) go does not matter.
     b->graphs.clear();
     for (size_t i = 0; i < b->members.size(); i++) {
         hf_ctx* m = b->members[i];
         m->graphs.clear();
-        if (b->planar_out) {   // the stages of the batch's planar outputs (idle: the batch stream was synchronised above)
-            for (void* p : m->period_stage) if (p) hipFree(p);
-            m->period_stage.clear();
-        }
+        if (b->planar_out) m->period_stage.clear();   // the stages of the batch's planar outputs
         m->stream = b->own_streams[i];
         m->warp_stream = b->own_warp_streams[i];
         m->on_warp_stream = false;
         m->batch = nullptr;
     }
-    for (hipStream_t ws : b->warp_streams) hipStreamDestroy(ws);
-    if (b->stream) hipStreamDestroy(b->stream);
-    for (hipEvent_t e : b->tl.events) hipEventDestroy(e);
-    if (b->tl.anchor) hipEventDestroy(b->tl.anchor);
-    if (b->scene_states) hipFree(b->scene_states);
-    if (b->scene_kinds) hipFree(b->scene_kinds);
-    if (b->scene_records) hipHostFree(b->scene_records);
     delete b;
 }
 
@@ -241,7 +223,7 @@ int batch_calculate(hf_batch* b, bool warmup_keeps_flow) {
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     if (int rc = batch_check_flow_params(b)) return rc;
     const bool observed = hf::t_launch_observer == &b->tl;
-    if (int rc = calculate_flow(b->members.data(), (int)b->members.size(), b->stream, observed ? nullptr : &b->graphs, warmup_keeps_flow))
+    if (int rc = calculate_flow(b->members.data(), (int)b->members.size(), b->stream.get(), observed ? nullptr : &b->graphs, warmup_keeps_flow))
         return batch_fail(b, rc == HF_ERR_OUT_OF_MEMORY ? HF_ERR_HIP : rc, l->err);   // (a batch has always reported a HIP error of its chain as HF_ERR_HIP)
     return HF_OK;
 }
@@ -317,7 +299,9 @@ int hf_batch_planar(const hf_batch* b) { return b ? (b->planar_in ? 1 : 0) | (b-
 // ---- timeline: start / stop of every dispatch of a batch on the device's clock, no profiler attached ----
 namespace {
 std::mutex g_tl_mutex;
-std::map<int, hipEvent_t> g_tl_reference;   // per device: the zero of every batch's timeline in this process
+// per device: the zero of every batch's timeline in this process.  The one deliberate exception to hf_ctx.h's ownership rule: the events
+// live as long as the process, so they stay raw, are never released and are not counted by hf_debug_live_resources.
+std::map<int, hipEvent_t> g_tl_reference;
 }
 int hf_batch_timeline_enable(hf_batch* b, int max_launches, int skip_periods) {
     if (!b) return batch_fail(nullptr, HF_ERR_INVALID_ARGUMENT, "null batch");
@@ -325,37 +309,37 @@ int hf_batch_timeline_enable(hf_batch* b, int max_launches, int skip_periods) {
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     if (max_launches < 0 || max_launches > (1 << 20) || skip_periods < 0 || (max_launches > 0 && max_launches < 32))
         return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_timeline_enable: max_launches must be 0 or in [32, 2^20] (a period needs up to 32 free records), skip_periods >= 0");
-    if (hipStreamSynchronize(b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");
+    if (hipStreamSynchronize(b->stream.get()) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");
     b->tl.active = false;
     b->tl.recs.clear();
     b->tl.period = 0;
     b->tl.dropped = 0;
     b->tl.capacity = 0;
     if (max_launches == 0) {
-        for (hipEvent_t e : b->tl.events) hipEventDestroy(e);
         b->tl.events.clear();
         return HF_OK;
     }
     {
         std::lock_guard<std::mutex> lock(g_tl_mutex);
         if (!g_tl_reference.count(l->device)) {
-            hipEvent_t ref = nullptr;
-            if (hipEventCreate(&ref) != hipSuccess || hipEventRecord(ref, b->stream) != hipSuccess || hipEventSynchronize(ref) != hipSuccess)
+            Event ref;   // an owner until it is recorded, so that a failure releases it; then the process's (release(): uncounted from there on)
+            if (create_event(ref) != hipSuccess || hipEventRecord(ref.get(), b->stream.get()) != hipSuccess || hipEventSynchronize(ref.get()) != hipSuccess)
                 return batch_fail(b, HF_ERR_HIP, "hf_batch_timeline_enable: cannot record the reference event");
-            g_tl_reference[l->device] = ref;
+            g_tl_reference[l->device] = ref.release();
+            count_live(kLiveEvents, -1);
         }
         // This recording's own anchor on the reference's clock.  hipEventElapsedTime is a float: minutes after the reference it resolves
         // tens of microseconds, so a record is read against the anchor (a short, exact span) and only the anchor against the reference.
         float anchor_ms = 0.f;
-        if ((!b->tl.anchor && hipEventCreate(&b->tl.anchor) != hipSuccess) || hipEventRecord(b->tl.anchor, b->stream) != hipSuccess ||
-            hipEventSynchronize(b->tl.anchor) != hipSuccess || hipEventElapsedTime(&anchor_ms, g_tl_reference[l->device], b->tl.anchor) != hipSuccess)
+        if ((!b->tl.anchor && create_event(b->tl.anchor) != hipSuccess) || hipEventRecord(b->tl.anchor.get(), b->stream.get()) != hipSuccess ||
+            hipEventSynchronize(b->tl.anchor.get()) != hipSuccess || hipEventElapsedTime(&anchor_ms, g_tl_reference[l->device], b->tl.anchor.get()) != hipSuccess)
             return batch_fail(b, HF_ERR_HIP, "hf_batch_timeline_enable: cannot record the anchor event");
         b->tl.anchor_ms = (double)anchor_ms;
     }
     while (b->tl.events.size() < 2 * (size_t)max_launches) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "hf_batch_timeline_enable: hipEventCreate failed");
-        b->tl.events.push_back(e);
+        Event e;
+        if (create_event(e) != hipSuccess) return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "hf_batch_timeline_enable: hipEventCreate failed");
+        b->tl.events.push_back(std::move(e));
     }
     b->tl.recs.reserve((size_t)max_launches);
     b->tl.capacity = (size_t)max_launches;
@@ -369,9 +353,9 @@ int hf_batch_timeline_read(hf_batch* b, hf_timeline_record* out, int capacity, i
     if (!n_records || (capacity > 0 && !out)) return batch_fail(b, HF_ERR_INVALID_ARGUMENT, "hf_batch_timeline_read: null argument");
     hf_ctx* l = b->members[0];
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    if (hipStreamSynchronize(b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");
-    for (hipStream_t ws : b->warp_streams)      // HF_FLAG_DUAL_STREAM members: the per-member warps of an observed period run there
-        if (hipStreamSynchronize(ws) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize (warp stream) failed");
+    if (hipStreamSynchronize(b->stream.get()) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");
+    for (const Stream& ws : b->warp_streams)      // HF_FLAG_DUAL_STREAM members: the per-member warps of an observed period run there
+        if (hipStreamSynchronize(ws.get()) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize (warp stream) failed");
     hipEvent_t ref = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_tl_mutex);
@@ -388,7 +372,7 @@ int hf_batch_timeline_read(hf_batch* b, hf_timeline_record* out, int capacity, i
         std::memset(&o, 0, sizeof(o));
         std::strncpy(o.kernel, r.name, sizeof(o.kernel) - 1);
         o.period = r.period;
-        if (hipEventElapsedTime(&t0, b->tl.anchor, r.b) != hipSuccess || hipEventElapsedTime(&t1, b->tl.anchor, r.e) != hipSuccess ||
+        if (hipEventElapsedTime(&t0, b->tl.anchor.get(), r.b) != hipSuccess || hipEventElapsedTime(&t1, b->tl.anchor.get(), r.e) != hipSuccess ||
             hipEventElapsedTime(&d, r.b, r.e) != hipSuccess) {
             (void)hipGetLastError();      // events of a launch that failed or never ran: flag the record, keep the others
             o.flags = 1;
@@ -419,24 +403,22 @@ int hf_batch_scene_set(hf_batch* b, int member, int64_t source_frame_time, int32
     if (hipSetDevice(l->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
     if (!b->scene_records) {   // first use: the members' histories and kinds on the device, their record rings in mapped host memory
         const size_t nrec = (size_t)hf::kMaxFlowBatch * hf_batch::kSceneRing;
-        hf::SceneState* st = nullptr;
-        int32_t* kinds = nullptr;
-        hf::SceneRecord* recs = nullptr, *recs_dev = nullptr;
-        const bool ok = hipMalloc((void**)&st, hf::kMaxFlowBatch * sizeof(hf::SceneState)) == hipSuccess &&
-                        hipMalloc((void**)&kinds, hf::kMaxFlowBatch * sizeof(int32_t)) == hipSuccess &&
-                        hipHostMalloc((void**)&recs, nrec * sizeof(hf::SceneRecord), hipHostMallocMapped) == hipSuccess &&
-                        hipHostGetDevicePointer((void**)&recs_dev, recs, 0) == hipSuccess &&
-                        hipMemsetAsync(st, 0, hf::kMaxFlowBatch * sizeof(hf::SceneState), b->stream) == hipSuccess &&
-                        hipMemsetAsync(kinds, 0, hf::kMaxFlowBatch * sizeof(int32_t), b->stream) == hipSuccess;
+        DevBuf<hf::SceneState> st;   // all or nothing: into the batch only when every step has succeeded
+        DevBuf<int32_t> kinds;
+        HostBuf<hf::SceneRecord> recs;
+        hf::SceneRecord* recs_dev = nullptr;
+        const bool ok = alloc_device(st, hf::kMaxFlowBatch * sizeof(hf::SceneState)) == hipSuccess &&
+                        alloc_device(kinds, hf::kMaxFlowBatch * sizeof(int32_t)) == hipSuccess &&
+                        alloc_host(recs, nrec * sizeof(hf::SceneRecord), hipHostMallocMapped) == hipSuccess &&
+                        hipHostGetDevicePointer((void**)&recs_dev, recs.get(), 0) == hipSuccess &&
+                        hipMemsetAsync(st.get(), 0, hf::kMaxFlowBatch * sizeof(hf::SceneState), b->stream.get()) == hipSuccess &&
+                        hipMemsetAsync(kinds.get(), 0, hf::kMaxFlowBatch * sizeof(int32_t), b->stream.get()) == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
-            if (st) hipFree(st);
-            if (kinds) hipFree(kinds);
-            if (recs) hipHostFree(recs);
             return batch_fail(b, HF_ERR_OUT_OF_MEMORY, "hf_batch_scene_set: cannot allocate the scene-change state");
         }
-        std::memset(recs, 0, nrec * sizeof(hf::SceneRecord));
-        b->scene_states = st; b->scene_kinds = kinds; b->scene_records = recs; b->scene_records_dev = recs_dev;
+        std::memset(recs.get(), 0, nrec * sizeof(hf::SceneRecord));
+        b->scene_states = std::move(st); b->scene_kinds = std::move(kinds); b->scene_records = std::move(recs); b->scene_records_dev = recs_dev;
         b->scene.assign((size_t)n, hf_batch::SceneMember{});
     }
     hf_batch::SceneMember& sm = b->scene[(size_t)member];
@@ -536,7 +518,7 @@ int batch_run_period_auto(hf_batch* b, const void* const* device_frames, int row
                 da.clear[m] = sm.clear ? 1 : 0;
                 da.force[m] = (int8_t)(force_kind ? force_kind[m] : -1);
             }
-            hf::launch_scene_decide(da, b->scene_states, b->scene_kinds, b->scene_records_dev, hf_batch::kSceneRing, b->stream);
+            hf::launch_scene_decide(da, b->scene_states.get(), b->scene_kinds.get(), b->scene_records_dev, hf_batch::kSceneRing, b->stream.get());
             if (hipGetLastError() != hipSuccess) return batch_fail(b, HF_ERR_HIP, "scene_decide launch failed");
             for (hf_batch::SceneMember& sm : b->scene) { sm.written++; sm.clear = false; }
         } else {
@@ -571,14 +553,14 @@ int hf_batch_scene_read(hf_batch* b, int member, hf_scene_record* out, int capac
     *n_records = 0;
     if (b->scene.empty()) return HF_OK;
     if (hipSetDevice(b->members[0]->device) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipSetDevice failed");
-    if (hipStreamSynchronize(b->stream) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");   // (a no-op after hf_batch_sync)
+    if (hipStreamSynchronize(b->stream.get()) != hipSuccess) return batch_fail(b, HF_ERR_HIP, "hipStreamSynchronize failed");   // (a no-op after hf_batch_sync)
     hf_batch::SceneMember& sm = b->scene[(size_t)member];
     const uint64_t have = sm.written - sm.read;
     *n_records = (int)have;   // how many there were; min(capacity, that) are handed out and leave the ring
     static_assert(sizeof(hf_scene_record) == sizeof(hf::SceneRecord), "hf_scene_record is hf::SceneRecord");
     const uint64_t k = have < (uint64_t)capacity ? have : (uint64_t)capacity;
     for (uint64_t i = 0; i < k; i++)
-        std::memcpy(&out[i], &b->scene_records[(size_t)member * hf_batch::kSceneRing + (size_t)((sm.read + i) % hf_batch::kSceneRing)], sizeof(hf_scene_record));
+        std::memcpy(&out[i], &b->scene_records.get()[(size_t)member * hf_batch::kSceneRing + (size_t)((sm.read + i) % hf_batch::kSceneRing)], sizeof(hf_scene_record));
     sm.read += k;
     return HF_OK;
 }

@@ -25,18 +25,18 @@ int enqueue_flow_chain(const hf_ctx* const* cs, int n, hipStream_t s) {
     for (int i = 0; i < n; i++) {
         const hf_ctx* m = cs[i];
         hf::FlowStep& f = a.s[i];
-        f.pp1 = m->pp[1];                                             // :79 frame N-1
-        f.pp2 = m->pp[2];                                             // :80 frame N
+        f.pp1 = m->pp[1].get();                                       // :79 frame N-1
+        f.pp2 = m->pp[2].get();                                       // :80 frame N
         f.pl = m->pl;
         f.total_delta = m->d_total_delta;
         f.R = c->p.search_radius;
         f.delta_scalar = c->p.delta_scalar;
         f.neighbor_scalar = c->p.neighbor_scalar;
         f.delta_divisor = (uint32_t)(g.lh * g.lw * (g.hdr ? 6 : 10));  // :93 / HDR :93
-        f.sadtab = m->sadtab; f.sad_nbx = m->sad_nbx; f.sad_nby = m->sad_nby;
-        f.tables_base = m->tables; f.sums_base = m->sums;
-        f.counters = c->counters;                                     // (a batch counts in its leader's)
-        f.still_count = m->still_count;
+        f.sadtab = m->sadtab.get(); f.sad_nbx = m->sad_nbx; f.sad_nby = m->sad_nby;
+        f.tables_base = m->tables.get(); f.sums_base = m->sums.get();
+        f.counters = c->counters.get();                               // (a batch counts in its leader's)
+        f.still_count = m->still_count.get();
     }
     hf::FlowLevel none{};
     hf::PendingArgmin pending[hf::kMaxFlowBatch] = {};   // large-window step whose argmin the next launch takes (hf_kernels.h)
@@ -74,7 +74,7 @@ int enqueue_flow_chain(const hf_ctx* const* cs, int n, hipStream_t s) {
                 f.axis = axis;
                 f.capture_delta = (k == 0 && axis == 0);          // :91
                 f.pend = pending[i];
-                if (!small) f.sums = m->sums + (size_t)step_index * m->sums_stride;
+                if (!small) f.sums = m->sums.get() + (size_t)step_index * m->sums_stride;
                 pending[i] = hf::PendingArgmin{};
             }
             // sad_read follows from the previous level's window size; what makes it right is that that level wrote the tables (windows 32 .. 4
@@ -103,10 +103,10 @@ int enqueue_flow_chain(const hf_ctx* const* cs, int n, hipStream_t s) {
     for (int i = 0; i < n; i++) {
         const hf_ctx* m = cs[i];
         bb.s[i].last = iters ? m->levels[iters - 1] : none;
-        bb.s[i].blurred = m->blurred[0];
-        bb.s[i].packed = m->blurred_xy[0];
-        bb.s[i].zero = any_big ? m->sums : nullptr;
-        bb.s[i].still_count = m->still_count;
+        bb.s[i].blurred = m->blurred[0].get();
+        bb.s[i].packed = m->blurred_xy[0].get();
+        bb.s[i].zero = any_big ? m->sums.get() : nullptr;
+        bb.s[i].still_count = m->still_count.get();
         bb.s[i].still_out = m->still_count ? m->d_total_delta + 1 : nullptr;
     }
     hf::launch_blur_flow(g, bb, c->cfg.blur_radius, (int)(c->sums_bytes / sizeof(uint32_t)), s);  // :115-116
@@ -132,7 +132,7 @@ bool choose_tab_mode(hf_ctx* const* cs, int n) {
     int have = 0;
     for (int i = 0; i < n; i++) {
         hf_ctx* m = cs[i];
-        const uint32_t raw = m->h_total_delta ? ((volatile uint32_t*)m->h_total_delta)[1] : 0xFFFFFFFFu;
+        const uint32_t raw = m->h_total_delta ? ((volatile uint32_t*)m->h_total_delta.get())[1] : 0xFFFFFFFFu;
         int n32 = 0;
         for (const hf::FlowLevel& L : m->levels) if (L.window == 32) n32 = L.nwx * L.nwy;
         if (raw != 0xFFFFFFFFu && n32 > 0) {
@@ -153,7 +153,7 @@ int ensure_older_planes(hf_ctx* const* cs, int n, hipStream_t s) {
     for (int i = 0; i < n; i++) {
         hf_ctx* m = cs[i];
         if (!m->plane_pending[1]) continue;
-        pb.frame[pb.n] = m->ring[1]; pb.pp[pb.n] = m->pp[1]; pb.n++;
+        pb.frame[pb.n] = m->ring[1]; pb.pp[pb.n] = m->pp[1].get(); pb.n++;
     }
     if (pb.n) {
         hf::launch_prep_frames(cs[0]->g, cs[0]->pl, pb, s);
@@ -168,7 +168,7 @@ void finish_flow_timing(hf_ctx* c) {
     if (!c->flow_timing_pending) return;
     c->flow_timing_pending = false;
     float ms = 0.f;
-    if (c->upload_recorded && hipEventElapsedTime(&ms, c->ev_upload, c->ev_flow_end) == hipSuccess)
+    if (c->upload_recorded && hipEventElapsedTime(&ms, c->ev_upload.get(), c->ev_flow_end.get()) == hipSuccess)
         c->ofc_calc_time = (double)ms / 1e3;
     if (c->ofc_count >= kCalcTimeInterval) {
         c->ofc_avg = c->ofc_sum / c->ofc_count;
@@ -190,12 +190,12 @@ int enter_warp_stream(hf_ctx* c) {
         // warpFrames reads frames N-2/N-1 and the PREVIOUS flow (blurred[0]); the chain that may have just been
         // enqueued on c->stream writes the OTHER flow buffer, so the warps only wait for the chain that produced
         // blurred[0] (recorded behind the uploads of both frames) and run side by side with the current one
-        HF_HIP(c, hipStreamWaitEvent(c->warp_stream, c->ev_flow[0], 0));
+        HF_HIP(c, hipStreamWaitEvent(c->warp_stream, c->ev_flow[0].get(), 0));
     } else {
         // no tagged flow yet (the filter warps as soon as m_frameCount >= 3, before a second flow calculation):
         // order the warps behind everything enqueued so far, uploads included
-        HF_HIP(c, hipEventRecord(c->ev_chain_done, c->stream));
-        HF_HIP(c, hipStreamWaitEvent(c->warp_stream, c->ev_chain_done, 0));
+        HF_HIP(c, hipEventRecord(c->ev_chain_done.get(), c->stream));
+        HF_HIP(c, hipStreamWaitEvent(c->warp_stream, c->ev_chain_done.get(), 0));
     }
     c->on_warp_stream = true;
     return HF_OK;
@@ -204,25 +204,17 @@ int enter_warp_stream(hf_ctx* c) {
 int leave_warp_stream(hf_ctx* c) {
     if (!c->on_warp_stream) return HF_OK;
     // ev_warps_done was recorded right behind this context's last warp launch
-    HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_warps_done, 0));
+    HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_warps_done.get(), 0));
     c->on_warp_stream = false;
     return HF_OK;
 }
 
 static void rotate_after_upload(hf_ctx* c) {
-    // opticalFlowCalcSDR.cpp:22-28 : [0] <- [1] <- [2] <- new ; frame_count++
-    void* f = c->ring[0];
-    void* fs = c->ring_store[0];
-    c->ring_store[0] = c->ring_store[1]; c->ring_store[1] = c->ring_store[2]; c->ring_store[2] = fs;
-    hipEvent_t es = c->ev_slot_prep[0];
-    c->ev_slot_prep[0] = c->ev_slot_prep[1]; c->ev_slot_prep[1] = c->ev_slot_prep[2]; c->ev_slot_prep[2] = es;
-    void* st = c->in_stage[0];   // (HF_FLAG_PLANAR_IN) the stage a slot was converted from travels with it: ev_slot_prep guards both
-    c->in_stage[0] = c->in_stage[1]; c->in_stage[1] = c->in_stage[2]; c->in_stage[2] = st;
-    uint32_t* pp = c->pp[0];
-    const bool pend = c->plane_pending[0];
-    c->ring[0] = c->ring[1]; c->pp[0] = c->pp[1]; c->plane_pending[0] = c->plane_pending[1];
-    c->ring[1] = c->ring[2]; c->pp[1] = c->pp[2]; c->plane_pending[1] = c->plane_pending[2];
-    c->ring[2] = f;          c->pp[2] = pp;       c->plane_pending[2] = pend;
+    // opticalFlowCalcSDR.cpp:22-28 : [0] <- [1] <- [2] <- new (the old [0]) ; frame_count++.  The owners move with their slots.
+    auto rotate = [](auto& a) { std::rotate(std::begin(a), std::begin(a) + 1, std::end(a)); };
+    rotate(c->ring); rotate(c->ring_store); rotate(c->pp); rotate(c->plane_pending);
+    rotate(c->ev_slot_prep);
+    rotate(c->in_stage);   // (HF_FLAG_PLANAR_IN) the stage a slot was converted from travels with it: ev_slot_prep guards both
     c->ring_phase = (c->ring_phase + 1) % 3;
     c->p.frame_count++;
 }
@@ -257,7 +249,7 @@ int update_frames(hf_batch* b, hf_ctx* const* cs, int n, const void* const* src,
     for (int i = 0; i < n; i++) {
         hf_ctx* c = cs[i];
         if (!c->timing()) continue;
-        if (int rc = hip(c, hipEventRecord(c->ev_upload, c->stream), "hipEventRecord")) return rc;
+        if (int rc = hip(c, hipEventRecord(c->ev_upload.get(), c->stream), "hipEventRecord")) return rc;
         c->upload_recorded = true;
     }
     hf::PrepBatch pb{};
@@ -266,20 +258,20 @@ int update_frames(hf_batch* b, hf_ctx* const* cs, int n, const void* const* src,
     for (int i = 0; i < n; i++) {
         hf_ctx* c = cs[i];
         const bool by_reference = how == FrameSource::DeviceRef && !planar;
-        c->ring[0] = by_reference ? const_cast<void*>(src[i]) : c->ring_store[0];
+        c->ring[0] = by_reference ? const_cast<void*>(src[i]) : c->ring_store[0].get();
         const void* from = src[i];   // where the re-layout reads a planar frame
         if (how == FrameSource::Staged) {   // the caller's H2D on io_in put it into the slot (planar: into the slot's stage, which is src[i])
-            if (int rc = hip(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0), "hipStreamWaitEvent")) return rc;
+            if (int rc = hip(c, hipStreamWaitEvent(c->stream, c->ev_h2d.get(), 0), "hipStreamWaitEvent")) return rc;
         } else if (how == FrameSource::Host && planar) {   // one H2D of the whole frame into the stage
-            if (int rc = hip(c, hipMemcpyAsync(c->in_stage[0], src[i], c->in_bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync")) return rc;
-            from = c->in_stage[0];
+            if (int rc = hip(c, hipMemcpyAsync(c->in_stage[0].get(), src[i], c->in_bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync")) return rc;
+            from = c->in_stage[0].get();
         } else if (!planar && !by_reference) {
             const hipMemcpyKind kind = how == FrameSource::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
             if (int rc = hip(c, hipMemcpyAsync(c->ring[0], src[i], c->in_bytes, kind, c->stream), "hipMemcpyAsync")) return rc;
         }
         pin[i] = hf::PlanarPair{from, c->ring[0]};
         pb.frame[i] = c->ring[0];
-        pb.pp[i] = c->pp[0];
+        pb.pp[i] = c->pp[0].get();
         c->plane_pending[0] = defer;
     }
     // (a lone context keeps the single-frame kernel: its argument block is a tenth of the pair table's, 0.3 us per launch at 2160p)
@@ -290,7 +282,7 @@ int update_frames(hf_batch* b, hf_ctx* const* cs, int n, const void* const* src,
     if (int rc = hip(l, hipGetLastError(), "the phase-plane launch")) return rc;
     for (int i = 0; i < n; i++) {
         hf_ctx* c = cs[i];
-        if (c->io_in) if (int rc = hip(c, hipEventRecord(c->ev_slot_prep[0], c->stream), "hipEventRecord")) return rc;
+        if (c->io_in) if (int rc = hip(c, hipEventRecord(c->ev_slot_prep[0].get(), c->stream), "hipEventRecord")) return rc;
         rotate_after_upload(c);
     }
     if (!b && !l->async() && how != FrameSource::Staged) return sync_ctx(l);
@@ -313,28 +305,24 @@ int after_flow_enqueued(hf_ctx* c, hipStream_t s) {
     c->last_iterations = iters;
     c->last_level = iters ? c->levels[iters - 1] : hf::FlowLevel{};
     if (c->timing()) {
-        HF_HIP(c, hipEventRecord(c->ev_flow_end, s));
+        HF_HIP(c, hipEventRecord(c->ev_flow_end.get(), s));
         c->flow_timing_pending = true;
     }
     c->delta_pending = c->last_iterations > 0;
     if (c->async() && !c->batch) {   // hf_wait_flow(): the host needs m_totalFrameDelta of THIS chain before it decides warp vs copy
-        if (!c->ev_flow_done) HF_HIP(c, hipEventCreateWithFlags(&c->ev_flow_done, hipEventDisableTiming));
-        HF_HIP(c, hipEventRecord(c->ev_flow_done, s));
+        if (!c->ev_flow_done) HF_HIP(c, create_event(c->ev_flow_done, hipEventDisableTiming));
+        HF_HIP(c, hipEventRecord(c->ev_flow_done.get(), s));
         c->flow_done_recorded = true;
     }
     if (c->dual()) {   // tag the flow buffer just written, the tag travels with the buffer through the swap below
-        HF_HIP(c, hipEventRecord(c->ev_flow[0], s));
+        HF_HIP(c, hipEventRecord(c->ev_flow[0].get(), s));
         c->ev_flow_valid[0] = true;
-        hipEvent_t te = c->ev_flow[0]; c->ev_flow[0] = c->ev_flow[1]; c->ev_flow[1] = te;
-        bool tv = c->ev_flow_valid[0]; c->ev_flow_valid[0] = c->ev_flow_valid[1]; c->ev_flow_valid[1] = tv;
+        std::swap(c->ev_flow[0], c->ev_flow[1]);
+        std::swap(c->ev_flow_valid[0], c->ev_flow_valid[1]);
     }
     // opticalFlowCalcSDR.cpp:121-123 : swap so that [1] = newest flow, [0] = previous flow
-    int16_t* t = c->blurred[0];
-    c->blurred[0] = c->blurred[1];
-    c->blurred[1] = t;
-    uint32_t* txy = c->blurred_xy[0];
-    c->blurred_xy[0] = c->blurred_xy[1];
-    c->blurred_xy[1] = txy;
+    std::swap(c->blurred[0], c->blurred[1]);
+    std::swap(c->blurred_xy[0], c->blurred_xy[1]);
     c->blur_phase ^= 1;
     c->have_flow = true;
     return HF_OK;
@@ -368,10 +356,11 @@ int calculate_flow(hf_ctx* const* cs, int n, hipStream_t s, ChainGraphs* graphs,
             capture_lock.unlock();
             if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
             HF_HIP(l, e);
-            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            GraphExec fresh;
+            const hipError_t ei = instantiate_graph(fresh, graph);
             hipGraphDestroy(graph);
             HF_HIP(l, ei);
-            graphs->insert(key, exec);
+            exec = graphs->insert(key, std::move(fresh));
         }
     }
     // the leader's profile carries the chain (one span = n chains); an observed launch carries the timeline's events, not a profile span's
@@ -403,7 +392,7 @@ void* copy_source(const hf_ctx* c) { return c->ring[c->p.frame_count >= 3 ? 0 : 
 
 // m_warpCalcTime (opticalFlowCalcSDR.cpp:36-41) runs from the first warp or copy launch after a download, on the stream the caller names
 static int mark_warp_start(hf_ctx* c, hipStream_t s) {
-    if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start, s)); c->warp_started = true; }
+    if (!c->warp_started && c->timing()) { HF_HIP(c, hipEventRecord(c->ev_warp_start.get(), s)); c->warp_started = true; }
     return HF_OK;
 }
 
@@ -411,22 +400,22 @@ static int mark_warp_start(hf_ctx* c, hipStream_t s) {
 // flow_index 1: the period is issued BEFORE the chain of its source period -- the previous flow is still the newest one
 static void fill_period(hf_ctx* c, int n, const float* t, void* const* outs, hf::WarpPeriod& p, int flow_index = 0) {
     p.frame12 = c->ring[0]; p.frame21 = c->ring[1];
-    p.flow = c->blurred[flow_index]; p.flow_xy = c->blurred_xy[flow_index];
+    p.flow = c->blurred[flow_index].get(); p.flow_xy = c->blurred_xy[flow_index].get();
     p.black = output_levels(c).black; p.white = output_levels(c).white;
     p.n_out = n;
-    p.counters = c->counters;
-    for (int i = 0; i < n; i++) { p.ts[i] = t[i]; p.outs[i] = outs[i] ? outs[i] : c->out_frame; }
+    p.counters = c->counters.get();
+    for (int i = 0; i < n; i++) { p.ts[i] = t[i]; p.outs[i] = outs[i] ? outs[i] : c->out_frame.get(); }
 }
 
 // The semi-planar frames the warps of a period write where its output side is planar (HF_FLAG_PLANAR_OUT; a member of a
 // HF_FLAG_BATCH_PLANAR_OUT batch) and the caller named a buffer: grown to the widest period seen, kMaxWarpOutputs at the most -- a wider
 // period goes out in chunks, each converted before the next one's warps reuse the stages (stream order).  Allocates, so a call runs it
-// before its first enqueue.  Freed by hf_batch_destroy for a batch's members, by hf_destroy otherwise.
+// before its first enqueue.  Released by hf_batch_destroy for a batch's members, with the context otherwise.
 int ensure_period_stages(hf_ctx* c, int n) {
     while ((int)c->period_stage.size() < n && (int)c->period_stage.size() < hf::kMaxWarpOutputs) {
-        void* p = nullptr;
-        HF_HIP(c, hipMalloc(&p, c->out_bytes));
-        c->period_stage.push_back(p);
+        DevBuf<void> p;
+        HF_HIP(c, alloc_device(p, c->out_bytes));
+        c->period_stage.push_back(std::move(p));
     }
     return HF_OK;
 }
@@ -444,14 +433,14 @@ static int warp_member(hf_ctx* c, const hf::WarpPeriod& p, int mode) {
     bool fused = false;
     if (fuse) {
         const int span = span_open(c, 0);
-        fused = hf::launch_warp_periods(c->g, 1, &p, mode, c->warp_stream, span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
+        fused = hf::launch_warp_periods(c->g, 1, &p, mode, c->warp_stream, span >= 0 ? c->spans[span].b.get() : nullptr, span >= 0 ? c->spans[span].e.get() : nullptr);
         if (!fused) span_cancel(c, span);   // shape not eligible: drop the unused span
         else if (span >= 0) c->spans[span].frames = n_out;
     }
     for (int i = 0; i < n_out && !fused; i++) {
         const int span = span_open(c, 0);
         hf::launch_warp(c->g, p.frame12, p.frame21, p.flow, p.flow_xy, p.outs[i], p.ts[i], mode, p.black, p.white, c->warp_stream,
-                        span >= 0 ? c->spans[span].b : nullptr, span >= 0 ? c->spans[span].e : nullptr);
+                        span >= 0 ? c->spans[span].b.get() : nullptr, span >= 0 ? c->spans[span].e.get() : nullptr);
     }
     HF_HIP(c, hipGetLastError());
     return note_launch(c, c->warp_stream);
@@ -508,7 +497,7 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
             void* outs[hf::kMaxWarpOutputs];
             for (int i = 0; i < count; i++) {
                 void* o = device_out[at + i];
-                outs[i] = o && planar ? c->period_stage[(size_t)i] : o;
+                outs[i] = o && planar ? c->period_stage[(size_t)i].get() : o;
                 if (o && planar) pairs[npairs++] = hf::PlanarPair{outs[i], o};
             }
             if (count) {
@@ -517,7 +506,7 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
             }
             if (copy) {   // the repair of the cut periods: this chunk's outputs of the members whose kind is copy
                 copy->m[m].n_out = count;
-                for (int i = 0; i < count; i++) copy->m[m].outs[i] = outs[i] ? outs[i] : c->out_frame;
+                for (int i = 0; i < count; i++) copy->m[m].outs[i] = outs[i] ? outs[i] : c->out_frame.get();
             }
         }
         bool done = np == 0 || !(parts & hf::kPartWarps);
@@ -526,12 +515,12 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
             // no asynchronous host I/O (hf_batch_create / hf_*_async enforce it): no output-ring slot to guard, no side stream to notify
             for (int k = 0; k < np; k++) {
                 hf_ctx* c = who[k];
-                if (before_chain && c->plane_pending[1]) periods[k].plane21 = c->pp[1];
+                if (before_chain && c->plane_pending[1]) periods[k].plane21 = c->pp[1].get();
                 if (int rc = mark_warp_start(c, l->stream)) return of_member(c, rc);
             }
             const int span = hf::t_launch_observer == &b->tl ? -1 : span_open(l, 0);   // (an observed launch carries the timeline's events, not a profile span's)
             bool built[hf::kMaxFlowBatch];
-            if (hf::launch_warp_periods(l->g, np, periods, mode, l->stream, span >= 0 ? l->spans[span].b : nullptr, span >= 0 ? l->spans[span].e : nullptr,
+            if (hf::launch_warp_periods(l->g, np, periods, mode, l->stream, span >= 0 ? l->spans[span].b.get() : nullptr, span >= 0 ? l->spans[span].e.get() : nullptr,
                                         before_chain ? &l->pl : nullptr, built)) {
                 if (span >= 0) l->spans[span].frames = frames;
                 if (launched) *launched = true;   // from here on the period's warps are enqueued: an error is final, never a reason to issue them again
@@ -547,7 +536,7 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
             for (int k = 0; k < np; k++) if (int rc = warp_member(who[k], periods[k], mode)) return of_member(who[k], rc);
         }
         if (copy && (parts & hf::kPartCopy)) {
-            hf::launch_scene_copy(l->g, *copy, b->scene_kinds, l->stream);
+            hf::launch_scene_copy(l->g, *copy, b->scene_kinds.get(), l->stream);
             if (hipGetLastError() != hipSuccess) return of_launch("scene_copy launch failed");
         }
         if (npairs && (parts & hf::kPartConvert)) {
@@ -558,7 +547,7 @@ int interpolate_period(hf_batch* b, hf_ctx* const* cs, int n, int row, const int
     // one completion event for all the warps (and conversions) the period put on a member's warp stream, behind the last of them
     for (int m = 0; m < n; m++)
         if (n_out[m] > 0 && cs[m]->on_warp_stream)
-            if (hipEventRecord(cs[m]->ev_warps_done, cs[m]->warp_stream) != hipSuccess) return of_launch("hipEventRecord failed");
+            if (hipEventRecord(cs[m]->ev_warps_done.get(), cs[m]->warp_stream) != hipSuccess) return of_launch("hipEventRecord failed");
     return HF_OK;
 }
 
@@ -570,9 +559,9 @@ int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind) {
             hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, c->out_target, dst, c->stream);
         } else {   // re-layout into the stage paired with the output slot, then one D2H
             if (int rc = ensure_out_stage(c)) return rc;
-            void* st = c->out_stage[out_slot(c, c->out_target)];
+            void* st = c->out_stage[out_slot(c, c->out_target)].get();
             if (c->dl_issued)   // an asynchronous readback (hf_download_frame_async) may still read that stage
-                HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_dl[(c->dl_issued - 1) % hf_ctx::kDlRing], 0));
+                HF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_dl[(c->dl_issued - 1) % hf_ctx::kDlRing].get(), 0));
             hf::launch_planar_out(c->g.hdr, c->g.H, c->g.out_stride, c->out_target, st, c->stream);
             HF_HIP(c, hipMemcpyAsync(dst, st, c->out_bytes, kind, c->stream));
         }
@@ -580,11 +569,11 @@ int download_common(hf_ctx* c, void* dst, hipMemcpyKind kind) {
     } else if (c->out_target != dst) {
         HF_HIP(c, hipMemcpyAsync(dst, c->out_target, c->out_bytes, kind, c->stream));
     }
-    if (c->timing()) HF_HIP(c, hipEventRecord(c->ev_warp_end, c->stream));
+    if (c->timing()) HF_HIP(c, hipEventRecord(c->ev_warp_end.get(), c->stream));
     if (kind == hipMemcpyDeviceToHost || !c->async()) {
         if (int rc = sync_ctx(c)) return rc;
         float ms = 0.f;
-        if (c->warp_started && hipEventElapsedTime(&ms, c->ev_warp_start, c->ev_warp_end) == hipSuccess)
+        if (c->warp_started && hipEventElapsedTime(&ms, c->ev_warp_start.get(), c->ev_warp_end.get()) == hipSuccess)
             c->warp_calc_time = (double)ms / 1e3;  // opticalFlowCalcSDR.cpp:36-41
     }
     c->warp_started = false;
@@ -623,7 +612,7 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
     hf::WarpPeriod p;   // frames N-2 / N-1 and the PREVIOUS flow (:154-156) into the output target
     fill_period(c, 1, &t, &c->out_target, p);
     if (int rc = warp_member(c, p, mode)) return rc;
-    if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done, c->warp_stream));
+    if (c->on_warp_stream) HF_HIP(c, hipEventRecord(c->ev_warps_done.get(), c->warp_stream));
     return HF_OK;
 }
 
@@ -679,7 +668,7 @@ int hf_set_output_buffer(hf_ctx* c, void* device_out) {
     HF_CHECK_CTX(c);
     if (device_out && c->planar_out())
         return fail(c, HF_ERR_STATE, "hf_set_output_buffer: the kernels write NV12 / P010 frames; under HF_FLAG_PLANAR_OUT use hf_download_frame_device");
-    c->out_target = device_out ? device_out : c->out_frame;
+    c->out_target = device_out ? device_out : c->out_frame.get();
     return HF_OK;
 }
 

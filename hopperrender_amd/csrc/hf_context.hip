@@ -12,6 +12,7 @@ thread_local std::string g_create_error;
 
 namespace hfi {
 std::shared_mutex g_capture_mutex;
+std::atomic<int64_t> g_live[kLiveKinds];
 }  // namespace hfi
 
 namespace hfi {
@@ -57,53 +58,50 @@ int effective_iterations(const hf_ctx* c) {
     return iters;
 }
 
-hipEvent_t pool_event(hf_ctx* c) {
-    if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+Event pool_event(hf_ctx* c) {   // empty: none could be created
+    Event e;
+    if (!c->ev_pool.empty()) { e = std::move(c->ev_pool.back()); c->ev_pool.pop_back(); }
+    else (void)create_event(e);
     return e;
 }
 
-// Opens a profiled span on the stream; returns the index of the span or -1.
-int span_begin(hf_ctx* c, int kind, hipStream_t stream) {
-    if (!c->profiling()) return -1;
-    if ((c->prof_seen[kind]++ % (unsigned)c->prof_every[kind]) != 0) return -1;
-    hf_ctx::Span s{pool_event(c), pool_event(c), kind, nullptr, 1};
-    if (!s.b || !s.e) return -1;
-    s.stream = stream ? stream : c->stream;
-    hipEventRecord(s.b, s.stream);
-    c->spans.push_back(s);
-    return (int)c->spans.size() - 1;
-}
-
-// Span whose two events are filled in by the launch itself (hipExtLaunchKernelGGL start/stop events).
+// Span whose two events are filled in by the launch itself (hipExtLaunchKernelGGL start/stop events); returns the index of the span or -1.
 int span_open(hf_ctx* c, int kind) {
     if (!c->profiling()) return -1;
     if ((c->prof_seen[kind]++ % (unsigned)c->prof_every[kind]) != 0) return -1;
     hf_ctx::Span s{pool_event(c), pool_event(c), kind, nullptr, 1};
-    if (!s.b || !s.e) return -1;
-    c->spans.push_back(s);
+    if (!s.b || !s.e) return -1;   // (the one that could be created goes with s)
+    c->spans.push_back(std::move(s));
     return (int)c->spans.size() - 1;
 }
 
+// Opens a profiled span on the stream: its begin event is recorded here, its end event by span_end.
+int span_begin(hf_ctx* c, int kind, hipStream_t stream) {
+    const int idx = span_open(c, kind);
+    if (idx < 0) return -1;
+    c->spans[idx].stream = stream ? stream : c->stream;
+    hipEventRecord(c->spans[idx].b.get(), c->spans[idx].stream);
+    return idx;
+}
+
 void span_end(hf_ctx* c, int idx) {
-    if (idx >= 0) hipEventRecord(c->spans[idx].e, c->spans[idx].stream);
+    if (idx >= 0) hipEventRecord(c->spans[idx].e.get(), c->spans[idx].stream);
 }
 
 void span_cancel(hf_ctx* c, int idx) {   // gives back the events of the span opened last, whose launch did not happen
-    if (idx >= 0) { c->ev_pool.push_back(c->spans[idx].b); c->ev_pool.push_back(c->spans[idx].e); c->spans.pop_back(); }
+    if (idx >= 0) { c->ev_pool.push_back(std::move(c->spans[idx].b)); c->ev_pool.push_back(std::move(c->spans[idx].e)); c->spans.pop_back(); }
 }
 
 void collect_spans(hf_ctx* c) {  // stream must be idle
     for (auto& s : c->spans) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s.b, s.e) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, s.b.get(), s.e.get()) == hipSuccess) {
             if (s.kind == 0) { c->prof.warp_launches++; c->prof.warp_ms += ms; c->prof.warp_frames += (uint64_t)s.frames; }
             else if (s.kind == 1) { c->prof.copy_launches++; c->prof.copy_ms += ms; }
             else { c->prof.flow_chains += (uint64_t)s.frames; c->prof.flow_ms += ms; }   // a batch span covers n chains
         }
-        c->ev_pool.push_back(s.b);
-        c->ev_pool.push_back(s.e);
+        c->ev_pool.push_back(std::move(s.b));
+        c->ev_pool.push_back(std::move(s.e));
     }
     c->spans.clear();
 }
@@ -111,7 +109,7 @@ void collect_spans(hf_ctx* c) {  // stream must be idle
 int sync_ctx(hf_ctx* c) {
     if (int rc = leave_warp_stream(c)) return rc;
     HF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->io_in) { HF_HIP(c, hipStreamSynchronize(c->io_in)); HF_HIP(c, hipStreamSynchronize(c->io_out)); }
+    if (c->io_in) { HF_HIP(c, hipStreamSynchronize(c->io_in.get())); HF_HIP(c, hipStreamSynchronize(c->io_out.get())); }
     collect_spans(c);
     if (c->delta_pending) { c->total_frame_delta = *c->h_total_delta; c->delta_pending = false; }
     finish_flow_timing(c);
@@ -283,62 +281,57 @@ int hf_create(const hf_config* cfg, hf_ctx** out_ctx) {
 #define HF_TRY(call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
         fail(c, _e == hipErrorOutOfMemory ? HF_ERR_OUT_OF_MEMORY : HF_ERR_HIP, "HIP error %d (%s) in %s", (int)_e, hipGetErrorString(_e), #call); \
         return bail(_e == hipErrorOutOfMemory ? HF_ERR_OUT_OF_MEMORY : HF_ERR_HIP); } } while (0)
-    HF_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HF_TRY(create_stream(c->own_stream));
+    c->stream = c->own_stream.get();
     if (cfg->flags & HF_FLAG_DUAL_STREAM) {
-        HF_TRY(hipStreamCreateWithFlags(&c->own_warp_stream, hipStreamNonBlocking));
-        HF_TRY(hipEventCreateWithFlags(&c->ev_flow[0], hipEventDisableTiming));
-        HF_TRY(hipEventCreateWithFlags(&c->ev_flow[1], hipEventDisableTiming));
+        HF_TRY(create_stream(c->own_warp_stream));
+        HF_TRY(create_event(c->ev_flow[0], hipEventDisableTiming));
+        HF_TRY(create_event(c->ev_flow[1], hipEventDisableTiming));
     }
-    c->own_stream = c->stream;
-    c->warp_stream = c->own_warp_stream ? c->own_warp_stream : c->stream;
-    HF_TRY(hipEventCreateWithFlags(&c->ev_chain_done, hipEventDisableTiming));
-    HF_TRY(hipEventCreateWithFlags(&c->ev_warps_done, hipEventDisableTiming));
+    c->warp_stream = c->own_warp_stream ? c->own_warp_stream.get() : c->stream;
+    HF_TRY(create_event(c->ev_chain_done, hipEventDisableTiming));
+    HF_TRY(create_event(c->ev_warps_done, hipEventDisableTiming));
     for (int i = 0; i < 3; i++) {
-        HF_TRY(hipMalloc(&c->ring_store[i], c->in_bytes));
-        c->ring[i] = c->ring_store[i];
-        HF_TRY(hipMalloc((void**)&c->pp[i], c->pl.bytes));
+        HF_TRY(alloc_device(c->ring_store[i], c->in_bytes));
+        c->ring[i] = c->ring_store[i].get();
+        HF_TRY(alloc_device(c->pp[i], c->pl.bytes));
         HF_TRY(hipMemsetAsync(c->ring[i], 0, c->in_bytes, c->stream));
-        HF_TRY(hipMemsetAsync(c->pp[i], 0, c->pl.bytes, c->stream));
+        HF_TRY(hipMemsetAsync(c->pp[i].get(), 0, c->pl.bytes, c->stream));
     }
-    HF_TRY(hipMalloc(&c->out_frame, c->out_bytes));
-    HF_TRY(hipMemsetAsync(c->out_frame, 0, c->out_bytes, c->stream));
-    c->out_target = c->out_frame;
-    HF_TRY(hipMalloc((void**)&c->tables, c->tables_bytes));
-    HF_TRY(hipMemsetAsync(c->tables, 0, c->tables_bytes, c->stream));
+    HF_TRY(alloc_device(c->out_frame, c->out_bytes));
+    HF_TRY(hipMemsetAsync(c->out_frame.get(), 0, c->out_bytes, c->stream));
+    c->out_target = c->out_frame.get();
+    HF_TRY(alloc_device(c->tables, c->tables_bytes));
+    HF_TRY(hipMemsetAsync(c->tables.get(), 0, c->tables_bytes, c->stream));
     {
         size_t o = 0;
         for (auto& L : c->levels) {
-            L.tx = c->tables + o; o += (size_t)L.nwx * L.nwy;
-            L.ty = c->tables + o; o += (size_t)L.nwx * L.nwy;
+            L.tx = c->tables.get() + o; o += (size_t)L.nwx * L.nwy;
+            L.ty = c->tables.get() + o; o += (size_t)L.nwx * L.nwy;
         }
     }
-    HF_TRY(hipMalloc((void**)&c->off_view, 2 * c->plane_elems * sizeof(int16_t)));
+    HF_TRY(alloc_device(c->off_view, 2 * c->plane_elems * sizeof(int16_t)));
     for (int i = 0; i < 2; i++) {
-        HF_TRY(hipMalloc((void**)&c->blurred[i], 2 * c->plane_elems * sizeof(int16_t)));
-        HF_TRY(hipMemsetAsync(c->blurred[i], 0, 2 * c->plane_elems * sizeof(int16_t), c->stream));
-        HF_TRY(hipMalloc((void**)&c->blurred_xy[i], c->plane_elems * sizeof(uint32_t)));
-        HF_TRY(hipMemsetAsync(c->blurred_xy[i], 0, c->plane_elems * sizeof(uint32_t), c->stream));
+        HF_TRY(alloc_device(c->blurred[i], 2 * c->plane_elems * sizeof(int16_t)));
+        HF_TRY(hipMemsetAsync(c->blurred[i].get(), 0, 2 * c->plane_elems * sizeof(int16_t), c->stream));
+        HF_TRY(alloc_device(c->blurred_xy[i], c->plane_elems * sizeof(uint32_t)));
+        HF_TRY(hipMemsetAsync(c->blurred_xy[i].get(), 0, c->plane_elems * sizeof(uint32_t), c->stream));
     }
     if (c->sadtab_bytes) {
-        HF_TRY(hipMalloc((void**)&c->sadtab, c->sadtab_bytes));
-        HF_TRY(hipMalloc((void**)&c->still_count, 64));
-        HF_TRY(hipMemsetAsync(c->still_count, 0, 64, c->stream));
+        HF_TRY(alloc_device(c->sadtab, c->sadtab_bytes));
+        HF_TRY(alloc_device(c->still_count, 64));
+        HF_TRY(hipMemsetAsync(c->still_count.get(), 0, 64, c->stream));
     }   // (every entry is written before it is read inside a chain)
-    HF_TRY(hipMalloc((void**)&c->sums, c->sums_bytes));
-    HF_TRY(hipMemsetAsync(c->sums, 0, c->sums_bytes, c->stream));
-    HF_TRY(hipMalloc((void**)&c->d_probe, 64 * sizeof(float)));
+    HF_TRY(alloc_device(c->sums, c->sums_bytes));
+    HF_TRY(hipMemsetAsync(c->sums.get(), 0, c->sums_bytes, c->stream));
+    HF_TRY(alloc_device(c->d_probe, 64 * sizeof(float)));
     // m_totalFrameDelta is stored by the chain straight into mapped pinned memory (reference: blocking 4-byte
     // readback in the middle of the chain, opticalFlowCalcSDR.cpp:91-94)
-    HF_TRY(hipHostMalloc((void**)&c->h_total_delta, 64, hipHostMallocMapped));
-    *c->h_total_delta = 0;
-    c->h_total_delta[1] = 0xFFFFFFFFu;                  // (no chain has published its content hint yet)
-    HF_TRY(hipHostGetDevicePointer((void**)&c->d_total_delta, c->h_total_delta, 0));
-    HF_TRY(hipEventCreate(&c->ev_upload));
-    HF_TRY(hipEventCreate(&c->ev_flow_end));
-    HF_TRY(hipEventCreate(&c->ev_warp_start));
-    HF_TRY(hipEventCreate(&c->ev_warp_end));
-    HF_TRY(hipEventCreate(&c->ev_user0));
-    HF_TRY(hipEventCreate(&c->ev_user1));
+    HF_TRY(alloc_host(c->h_total_delta, 64, hipHostMallocMapped));
+    c->h_total_delta.get()[0] = 0;
+    c->h_total_delta.get()[1] = 0xFFFFFFFFu;            // (no chain has published its content hint yet)
+    HF_TRY(hipHostGetDevicePointer((void**)&c->d_total_delta, c->h_total_delta.get(), 0));
+    for (Event* e : {&c->ev_upload, &c->ev_flow_end, &c->ev_warp_start, &c->ev_warp_end, &c->ev_user0, &c->ev_user1}) HF_TRY(create_event(*e));
     HF_TRY(hipStreamSynchronize(c->stream));
 #undef HF_TRY
     *out_ctx = c;
@@ -349,38 +342,10 @@ void hf_destroy(hf_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) { leave_warp_stream(c); hipStreamSynchronize(c->stream); }  // clFinish (opticalFlowCalcSDR.cpp:186)
+    if (c->io_in) { hipStreamSynchronize(c->io_in.get()); hipStreamSynchronize(c->io_out.get()); }
+    // Nothing of this context is in flight from here on, which is why the order in which its members release what they own (hf_ctx.h: every
+    // buffer, stream and event of it is held by an owner) does not matter.  c->stream may be a batch's shared stream: a view, not ours.
     c->graphs.clear();
-    for (int i = 0; i < 3; i++) { if (c->ring_store[i]) hipFree(c->ring_store[i]); if (c->pp[i]) hipFree(c->pp[i]); }
-    if (c->tables) hipFree(c->tables);
-    if (c->off_view) hipFree(c->off_view);
-    if (c->out_frame) hipFree(c->out_frame);
-    for (int i = 0; i < 2; i++) { if (c->blurred[i]) hipFree(c->blurred[i]); if (c->blurred_xy[i]) hipFree(c->blurred_xy[i]); }
-    if (c->sums) hipFree(c->sums);
-    if (c->sadtab) hipFree(c->sadtab);
-    if (c->still_count) hipFree(c->still_count);
-    if (c->counters) hipFree(c->counters);
-    if (c->d_probe) hipFree(c->d_probe);
-    if (c->error_slots) hipFree(c->error_slots);
-    if (c->h_total_delta) hipHostFree(c->h_total_delta);
-    for (auto& sp : c->spans) { hipEventDestroy(sp.b); hipEventDestroy(sp.e); }
-    for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
-    if (c->io_in) { hipStreamSynchronize(c->io_in); hipStreamSynchronize(c->io_out); hipStreamDestroy(c->io_in); hipStreamDestroy(c->io_out); }
-    for (int i = 1; i < hf_ctx::kOutRing; i++) if (c->out_ring[i]) hipFree(c->out_ring[i]);
-    for (void* p : c->in_stage) if (p) hipFree(p);
-    for (void* p : c->out_stage) if (p) hipFree(p);
-    for (void* p : c->period_stage) if (p) hipFree(p);
-    for (hipEvent_t e : {c->ev_h2d, c->ev_last_launch, c->ev_out_ready}) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_slot_prep) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_d2h) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_dl) if (e) hipEventDestroy(e);
-    if (c->ev_flow_done) hipEventDestroy(c->ev_flow_done);
-    for (hipEvent_t e : c->ev_flow) if (e) hipEventDestroy(e);
-    if (c->ev_chain_done) hipEventDestroy(c->ev_chain_done);
-    if (c->ev_warps_done) hipEventDestroy(c->ev_warps_done);
-    hipEvent_t evs[] = {c->ev_upload, c->ev_flow_end, c->ev_warp_start, c->ev_warp_end, c->ev_user0, c->ev_user1};
-    for (hipEvent_t e : evs) if (e) hipEventDestroy(e);
-    if (c->own_warp_stream) hipStreamDestroy(c->own_warp_stream);
-    if (c->own_stream) hipStreamDestroy(c->own_stream);   // c->stream may be a batch's shared stream (not ours)
     delete c;
 }
 
@@ -460,8 +425,8 @@ int hf_read_offsets(hf_ctx* c, int16_t* host_out) {
     if (!host_out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_read_offsets: null");
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
-    hf::launch_expand_offsets(c->g, c->last_level, c->off_view, c->stream);
-    HF_HIP(c, hipMemcpyAsync(host_out, c->off_view, 2 * c->plane_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    hf::launch_expand_offsets(c->g, c->last_level, c->off_view.get(), c->stream);
+    HF_HIP(c, hipMemcpyAsync(host_out, c->off_view.get(), 2 * c->plane_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HF_HIP(c, hipStreamSynchronize(c->stream));
     return HF_OK;
 }
@@ -471,7 +436,7 @@ int hf_read_blurred_flow(hf_ctx* c, int idx, int16_t* host_out) {
     if (!host_out || idx < 0 || idx > 1) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_read_blurred_flow: bad argument");
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(host_out, c->blurred[idx], 2 * c->plane_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HF_HIP(c, hipMemcpyAsync(host_out, c->blurred[idx].get(), 2 * c->plane_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HF_HIP(c, hipStreamSynchronize(c->stream));
     return HF_OK;
 }
@@ -481,7 +446,7 @@ int hf_read_phase_plane(hf_ctx* c, int ring_slot, void* host_out, int* complete)
     if (!host_out || ring_slot < 0 || ring_slot > 2) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_read_phase_plane: bad argument");
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(host_out, c->pp[ring_slot], c->pl.bytes, hipMemcpyDeviceToHost, c->stream));
+    HF_HIP(c, hipMemcpyAsync(host_out, c->pp[ring_slot].get(), c->pl.bytes, hipMemcpyDeviceToHost, c->stream));
     HF_HIP(c, hipStreamSynchronize(c->stream));
     if (complete) *complete = c->plane_pending[ring_slot] ? 0 : 1;
     return HF_OK;
@@ -492,8 +457,8 @@ int hf_write_blurred_flow(hf_ctx* c, int idx, const int16_t* host_in) {
     if (!host_in || idx < 0 || idx > 1) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_write_blurred_flow: bad argument");
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(c->blurred[idx], host_in, 2 * c->plane_elems * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-    hf::launch_pack_flow(c->g, c->blurred[idx], c->blurred_xy[idx], c->stream);
+    HF_HIP(c, hipMemcpyAsync(c->blurred[idx].get(), host_in, 2 * c->plane_elems * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    hf::launch_pack_flow(c->g, c->blurred[idx].get(), c->blurred_xy[idx].get(), c->stream);
     HF_HIP(c, hipStreamSynchronize(c->stream));
     return HF_OK;
 }
@@ -502,7 +467,7 @@ int hf_timer_begin(hf_ctx* c) {
     HF_CHECK_CTX(c);
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
-    HF_HIP(c, hipEventRecord(c->ev_user0, c->stream));
+    HF_HIP(c, hipEventRecord(c->ev_user0.get(), c->stream));
     return HF_OK;
 }
 
@@ -511,9 +476,9 @@ int hf_timer_end(hf_ctx* c, float* elapsed_ms) {
     if (!elapsed_ms) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_timer_end: null");
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
-    HF_HIP(c, hipEventRecord(c->ev_user1, c->stream));
-    HF_HIP(c, hipEventSynchronize(c->ev_user1));
-    HF_HIP(c, hipEventElapsedTime(elapsed_ms, c->ev_user0, c->ev_user1));
+    HF_HIP(c, hipEventRecord(c->ev_user1.get(), c->stream));
+    HF_HIP(c, hipEventSynchronize(c->ev_user1.get()));
+    HF_HIP(c, hipEventElapsedTime(elapsed_ms, c->ev_user0.get(), c->ev_user1.get()));
     return HF_OK;
 }
 
@@ -525,11 +490,11 @@ int hf_debug_counters_enable(hf_ctx* c, int on) {
     c->graphs.clear();
     if (c->batch) c->batch->graphs.clear();
     if (on) {
-        if (!c->counters) HF_HIP(c, hipMalloc((void**)&c->counters, hf::kCounterWords * sizeof(uint32_t)));
-        HF_HIP(c, hipMemsetAsync(c->counters, 0, hf::kCounterWords * sizeof(uint32_t), c->stream));
+        if (!c->counters) HF_HIP(c, alloc_device(c->counters, hf::kCounterWords * sizeof(uint32_t)));
+        HF_HIP(c, hipMemsetAsync(c->counters.get(), 0, hf::kCounterWords * sizeof(uint32_t), c->stream));
         return sync_ctx(c);
     }
-    if (c->counters) { hipFree(c->counters); c->counters = nullptr; }
+    c->counters.reset();
     return HF_OK;
 }
 
@@ -540,8 +505,8 @@ int hf_debug_counters_read(hf_ctx* c, hf_debug_counters* out, int reset) {
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
     uint32_t w[hf::kCounterWords];
-    HF_HIP(c, hipMemcpy(w, c->counters, sizeof(w), hipMemcpyDeviceToHost));
-    if (reset) HF_HIP(c, hipMemset(c->counters, 0, sizeof(w)));
+    HF_HIP(c, hipMemcpy(w, c->counters.get(), sizeof(w), hipMemcpyDeviceToHost));
+    if (reset) HF_HIP(c, hipMemset(c->counters.get(), 0, sizeof(w)));
     memset(out, 0, sizeof(*out));
     for (int i = 0; i < 3; i++) out->warp_workgroups[i] = w[hf::kCounterWarp + i];
     for (int k = 0; k < 16; k++) {
@@ -572,12 +537,10 @@ int hf_debug_bounds_selftest(hf_ctx* c) {
     if (!c) return HF_ERR_INVALID_ARGUMENT;
     uint32_t before = 0, after = 0, first[4] = {0, 0, 0, 0};
     if (int rc = hf_debug_bounds_violations(c, &before, nullptr, 0)) return rc;
-    int* scratch = nullptr;
-    if (hipMalloc(&scratch, 80 * sizeof(int)) != hipSuccess) return fail(c, HF_ERR_OUT_OF_MEMORY, "hf_debug_bounds_selftest: hipMalloc failed");
-    hf::launch_bounds_selftest(scratch, c->stream);
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(scratch);
-    if (e != hipSuccess) return fail(c, HF_ERR_HIP, "hf_debug_bounds_selftest: launch failed");
+    DevBuf<int> scratch;
+    if (alloc_device(scratch, 80 * sizeof(int)) != hipSuccess) return fail(c, HF_ERR_OUT_OF_MEMORY, "hf_debug_bounds_selftest: hipMalloc failed");
+    hf::launch_bounds_selftest(scratch.get(), c->stream);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, HF_ERR_HIP, "hf_debug_bounds_selftest: launch failed");
     if (int rc = hf_debug_bounds_violations(c, &after, first, 0)) return rc;
     if (after - before != 64u || (before == 0 && first[0] != 999u))
         return fail(c, HF_ERR_STATE, "hf_debug_bounds_selftest: 64 out-of-range indices were issued, %u recorded (first site %u)", after - before, first[0]);
@@ -589,9 +552,9 @@ int hf_device_rcp(hf_ctx* c, const float* host_in, float* host_out, int n) {
     if (!host_in || !host_out || n < 1 || n > 32) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_device_rcp: bad argument");
     if (int rc = set_device(c)) return rc;
     if (int rc = sync_ctx(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(c->d_probe, host_in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hf::launch_rcp_probe(c->d_probe, c->d_probe + 32, n, c->stream);
-    HF_HIP(c, hipMemcpyAsync(host_out, c->d_probe + 32, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HF_HIP(c, hipMemcpyAsync(c->d_probe.get(), host_in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hf::launch_rcp_probe(c->d_probe.get(), c->d_probe.get() + 32, n, c->stream);
+    HF_HIP(c, hipMemcpyAsync(host_out, c->d_probe.get() + 32, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HF_HIP(c, hipStreamSynchronize(c->stream));
     return HF_OK;
 }
@@ -613,20 +576,15 @@ int hf_clock_probe(int device_index, int duration_us, double* shader_mhz) {
     if (!shader_mhz || duration_us < 10 || duration_us > 100000) return fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_clock_probe: bad argument");
     *shader_mhz = 0.0;
     if (hipSetDevice(device_index) != hipSuccess) return fail(nullptr, HF_ERR_NO_DEVICE, "hf_clock_probe: bad device %d", device_index);
-    unsigned long long* res = nullptr;
-    hipStream_t s = nullptr;
-    if (hipHostMalloc((void**)&res, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return fail(nullptr, HF_ERR_OUT_OF_MEMORY, "hf_clock_probe: hipHostMalloc failed");
-    res[0] = res[1] = 0;
-    int rc = HF_OK;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) rc = fail(nullptr, HF_ERR_HIP, "hf_clock_probe: cannot create a stream");
-    if (rc == HF_OK) {
-        clock_probe_kernel<<<1, 64, 0, s>>>((unsigned long long)duration_us * 100ull, res);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = fail(nullptr, HF_ERR_HIP, "hf_clock_probe: launch failed");
-    }
-    if (rc == HF_OK && res[1] > 0) *shader_mhz = (double)res[0] / ((double)res[1] / 100.0);
-    if (s) hipStreamDestroy(s);
-    hipHostFree(res);
-    return rc;
+    HostBuf<unsigned long long> res;
+    Stream s;
+    if (alloc_host(res, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return fail(nullptr, HF_ERR_OUT_OF_MEMORY, "hf_clock_probe: hipHostMalloc failed");
+    res.get()[0] = res.get()[1] = 0;
+    if (create_stream(s) != hipSuccess) return fail(nullptr, HF_ERR_HIP, "hf_clock_probe: cannot create a stream");
+    clock_probe_kernel<<<1, 64, 0, s.get()>>>((unsigned long long)duration_us * 100ull, res.get());
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s.get()) != hipSuccess) return fail(nullptr, HF_ERR_HIP, "hf_clock_probe: launch failed");
+    if (res.get()[1] > 0) *shader_mhz = (double)res.get()[0] / ((double)res.get()[1] / 100.0);
+    return HF_OK;
 }
 
 // ---- what this device's HBM sustains for a plain streaming copy (the yardstick a bandwidth-bound pipeline should be held against) ----
@@ -649,36 +607,28 @@ int hf_hbm_copy_probe(int device_index, size_t bytes, int repeats, double* read_
     *read_plus_write_GBps = 0.0;
     if (hipSetDevice(device_index) != hipSuccess) return fail(nullptr, HF_ERR_NO_DEVICE, "hf_hbm_copy_probe: bad device %d", device_index);
     bytes &= ~(size_t)15;
-    void *a = nullptr, *b = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = HF_OK;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) rc = fail(nullptr, HF_ERR_OUT_OF_MEMORY, "hf_hbm_copy_probe: hipMalloc failed");
-    if (rc == HF_OK && (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess))
-        rc = fail(nullptr, HF_ERR_HIP, "hf_hbm_copy_probe: stream / event creation failed");
-    if (rc == HF_OK) {
-        (void)hipMemsetAsync(a, 0x5A, bytes, s);
-        const size_t n16 = bytes / 16;
-        // one pass of four 16-byte elements per thread, no loop: measured fastest on MI355X (tools/ubench/copy_rate.hip, 2 GiB: 5.7 TB/s
-        // with 131,072 workgroups against 4.8-5.3 TB/s with 2,048-32,768 looping ones; plain or non-temporal, 1-8 loads in flight: +-3 %)
-        const unsigned blocks = (unsigned)((n16 + 1023) / 1024);
-        float best = 0.f;
-        for (int r = 0; r <= repeats && rc == HF_OK; r++) {      // (the first pass warms up)
-            (void)hipEventRecord(e0, s);
-            hbm_copy_probe_kernel<<<blocks, 256, 0, s>>>((const uint4*)a, (uint4*)b, n16);
-            (void)hipEventRecord(e1, s);
-            float ms = 0.f;
-            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(nullptr, HF_ERR_HIP, "hf_hbm_copy_probe: launch failed");
-            else if (r > 0 && ms > 0.f) { const float g = (float)(2.0 * (double)bytes / (ms * 1e-3) / 1e9); best = g > best ? g : best; }
-        }
-        *read_plus_write_GBps = (double)best;
+    DevBuf<uint4> a, b;
+    Stream s;
+    Event e0, e1;
+    if (alloc_device(a, bytes) != hipSuccess || alloc_device(b, bytes) != hipSuccess) return fail(nullptr, HF_ERR_OUT_OF_MEMORY, "hf_hbm_copy_probe: hipMalloc failed");
+    if (create_stream(s) != hipSuccess || create_event(e0) != hipSuccess || create_event(e1) != hipSuccess)
+        return fail(nullptr, HF_ERR_HIP, "hf_hbm_copy_probe: stream / event creation failed");
+    (void)hipMemsetAsync(a.get(), 0x5A, bytes, s.get());
+    const size_t n16 = bytes / 16;
+    // one pass of four 16-byte elements per thread, no loop: measured fastest on MI355X (tools/ubench/copy_rate.hip, 2 GiB: 5.7 TB/s
+    // with 131,072 workgroups against 4.8-5.3 TB/s with 2,048-32,768 looping ones; plain or non-temporal, 1-8 loads in flight: +-3 %)
+    const unsigned blocks = (unsigned)((n16 + 1023) / 1024);
+    float best = 0.f;
+    for (int r = 0; r <= repeats; r++) {      // (the first pass warms up)
+        (void)hipEventRecord(e0.get(), s.get());
+        hbm_copy_probe_kernel<<<blocks, 256, 0, s.get()>>>(a.get(), b.get(), n16);
+        (void)hipEventRecord(e1.get(), s.get());
+        float ms = 0.f;
+        if (hipEventSynchronize(e1.get()) != hipSuccess || hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) return fail(nullptr, HF_ERR_HIP, "hf_hbm_copy_probe: launch failed");
+        if (r > 0 && ms > 0.f) { const float g = (float)(2.0 * (double)bytes / (ms * 1e-3) / 1e9); best = g > best ? g : best; }
     }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (s) hipStreamDestroy(s);
-    if (a) hipFree(a);
-    if (b) hipFree(b);
-    return rc;
+    *read_plus_write_GBps = (double)best;
+    return HF_OK;
 }
 
 int hf_device_malloc(int device_index, size_t bytes, void** out) {
@@ -702,6 +652,13 @@ int hf_host_malloc_pinned(size_t bytes, void** out) {
 }
 
 int hf_host_free_pinned(void* p) { return hipHostFree(p) == hipSuccess ? HF_OK : HF_ERR_HIP; }
+
+int hf_debug_live_resources(hf_live_resources* out) {
+    if (!out) return fail(nullptr, HF_ERR_INVALID_ARGUMENT, "hf_debug_live_resources: null");
+    auto live = [](LiveKind k) { return g_live[k].load(std::memory_order_relaxed); };
+    *out = hf_live_resources{live(kLiveDeviceBuffers), live(kLivePinnedBuffers), live(kLiveStreams), live(kLiveEvents), live(kLiveGraphExecs)};
+    return HF_OK;
+}
 
 int hf_memcpy_h2d(int device_index, void* d, const void* h, size_t bytes) { return util_copy(device_index, d, h, bytes, hipMemcpyHostToDevice); }
 

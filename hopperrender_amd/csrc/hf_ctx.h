@@ -1,7 +1,7 @@
 // hopperrender_amd/csrc/hf_ctx.h -- internal: the context and batch objects behind the C ABI of include/hopperflow.h and the helpers the
 // translation units of that ABI share.  The ABI is split by concern:
 //   hf_context.hip   context lifetime and state: hf_create / hf_destroy (detectDevices, buffers: opticalFlowCalcSDR.cpp:206-325), parameters,
-//                    statistics, profiling spans, parity taps, device-memory helpers
+//                    statistics, profiling spans, parity taps, device-memory helpers, hf_debug_live_resources (the counts of the owners below)
 //   hf_calc.hip      the five virtuals of one context: updateFrame, calculateOpticalFlow (the refinement chain as a cached hipGraph), warpFrames,
 //                    copyFrame, downloadFrame, and the fused period calls.  update_frames() there is the ONE host path of a frame update, for
 //                    n >= 1 contexts: hf_update_frame / _device / _device_ref and, behind its own H2D, hf_update_frame_async are its n = 1
@@ -26,19 +26,29 @@
 //   * m_totalFrameDelta is produced on the device and copied to pinned memory inside the graph
 //     (reference: blocking 4-byte readback in the middle of the chain, opticalFlowCalcSDR.cpp:91-94);
 //   * the whole chain replays as one hipGraph, keyed by the scalars, the table mode and every context's ring / flow-buffer phase (ChainGraphs).
+//
+// OWNERSHIP, the one rule: a member or local of an owner type below (DevBuf, HostBuf, Stream, Event, GraphExec) is OURS -- created by the
+// kind's helper, released when the owner goes; a raw pointer or handle is a VIEW of something an owner (or the caller) holds.  Nothing
+// else in csrc/ creates or releases a device resource, but hf_device_malloc / hf_host_malloc_pinned and their frees (the caller's memory)
+// and the timeline's process-lifetime reference events (hf_batch.hip g_tl_reference).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <shared_mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/config.h"
@@ -56,6 +66,55 @@ static_assert(kMaxSearchRadius <= 16, "the chain kernels keep 16 candidates per 
 constexpr int kMaxSteps = 32;          // 2 * log2(max window)
 
 extern std::shared_mutex g_capture_mutex;   // shared: a stream capture is in progress; exclusive: a legacy-stream copy (util_copy)
+
+// ---- the owner types (the rule: top of this file).  Each kind has one creation helper, which returns the hipError_t and fills the owner
+// only on success, and one stateless deleter; both count the kind in g_live (hf_debug_live_resources, hf_context.hip).  Nothing on a
+// period's steady-state path creates or destroys a resource, so no hot call touches the counts. ----
+enum LiveKind { kLiveDeviceBuffers, kLivePinnedBuffers, kLiveStreams, kLiveEvents, kLiveGraphExecs, kLiveKinds };
+extern std::atomic<int64_t> g_live[kLiveKinds];
+inline void count_live(LiveKind k, int64_t d) { g_live[k].fetch_add(d, std::memory_order_relaxed); }
+
+template <LiveKind K, auto Release> struct Deleter { template <typename H> void operator()(H h) const { (void)Release(h); count_live(K, -1); } };
+using FreeDevice = Deleter<kLiveDeviceBuffers, hipFree>;
+template <typename T> using DevBuf = std::unique_ptr<T, FreeDevice>;                                    // device memory
+template <typename T> using HostBuf = std::unique_ptr<T, Deleter<kLivePinnedBuffers, hipHostFree>>;   // pinned or mapped host memory
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, Deleter<kLiveStreams, hipStreamDestroy>>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Deleter<kLiveEvents, hipEventDestroy>>;
+using GraphExec = std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, Deleter<kLiveGraphExecs, hipGraphExecDestroy>>;
+
+template <typename T>
+hipError_t alloc_device(DevBuf<T>& out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) { out.reset(static_cast<T*>(p)); count_live(kLiveDeviceBuffers, 1); }
+    return e;
+}
+template <typename T>
+hipError_t alloc_host(HostBuf<T>& out, size_t bytes, unsigned flags) {
+    void* p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes, flags);
+    if (e == hipSuccess) { out.reset(static_cast<T*>(p)); count_live(kLivePinnedBuffers, 1); }
+    return e;
+}
+// a non-blocking stream; priority: of that priority (hf_batch_create)
+inline hipError_t create_stream(Stream& out, const int* priority = nullptr) {
+    hipStream_t s = nullptr;
+    const hipError_t e = priority ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, *priority) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) { out.reset(s); count_live(kLiveStreams, 1); }
+    return e;
+}
+inline hipError_t create_event(Event& out, unsigned flags = hipEventDefault) {
+    hipEvent_t ev = nullptr;
+    const hipError_t e = hipEventCreateWithFlags(&ev, flags);
+    if (e == hipSuccess) { out.reset(ev); count_live(kLiveEvents, 1); }
+    return e;
+}
+inline hipError_t instantiate_graph(GraphExec& out, hipGraph_t graph) {
+    hipGraphExec_t x = nullptr;
+    const hipError_t e = hipGraphInstantiate(&x, graph, nullptr, nullptr, 0);
+    if (e == hipSuccess) { out.reset(x); count_live(kLiveGraphExecs, 1); }
+    return e;
+}
 }  // namespace hfi
 
 // The instantiated hipGraphs of the refinement chain of one context, or of one batch (hf_calc.hip calculate_flow).  What a capture bakes in,
@@ -69,10 +128,10 @@ extern std::shared_mutex g_capture_mutex;   // shared: a stream capture is in pr
 struct ChainGraphs {
     static constexpr size_t kMaxEntries = 96;     // bound of the cache (parameters poked by a settings UI): a full one starts over
     using Key = std::array<int, 4 + hf::kMaxFlowBatch>;   // R, delta scalar, neighbour scalar, table mode, then one phase per context, rest -1
-    std::map<Key, hipGraphExec_t> map;
-    hipGraphExec_t find(const Key& k) const { auto it = map.find(k); return it == map.end() ? nullptr : it->second; }
-    void insert(const Key& k, hipGraphExec_t exec) { if (map.size() >= kMaxEntries) clear(); map.emplace(k, exec); }
-    void clear() { for (auto& kv : map) hipGraphExecDestroy(kv.second); map.clear(); }
+    std::map<Key, hfi::GraphExec> map;
+    hipGraphExec_t find(const Key& k) const { auto it = map.find(k); return it == map.end() ? nullptr : it->second.get(); }
+    hipGraphExec_t insert(const Key& k, hfi::GraphExec exec) { if (map.size() >= kMaxEntries) clear(); return map.emplace(k, std::move(exec)).first->second.get(); }
+    void clear() { map.clear(); }
 };
 
 struct hf_ctx {
@@ -80,12 +139,12 @@ struct hf_ctx {
     hf_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;                      // stream the context issues on (a batch's shared stream while it is a member)
-    hipStream_t own_stream = nullptr;                  // the stream this context created and destroys
+    hfi::Stream own_stream;                            // the stream this context created
     hipStream_t warp_stream = nullptr;                 // == stream unless HF_FLAG_DUAL_STREAM
-    hipStream_t own_warp_stream = nullptr;             // HF_FLAG_DUAL_STREAM: this context's second stream
-    hipEvent_t ev_chain_done = nullptr, ev_warps_done = nullptr;
+    hfi::Stream own_warp_stream;                       // HF_FLAG_DUAL_STREAM: this context's second stream
+    hfi::Event ev_chain_done, ev_warps_done;
     struct hf_batch* batch = nullptr;                  // the batch this context is a member of
-    hipEvent_t ev_flow[2] = {nullptr, nullptr};        // recorded behind the chain that wrote blurred[i] (swapped with it)
+    hfi::Event ev_flow[2];                             // recorded behind the chain that wrote blurred[i] (swapped with it)
     bool ev_flow_valid[2] = {false, false};
     bool dual() const { return (cfg.flags & HF_FLAG_DUAL_STREAM) != 0; }
     bool on_warp_stream = false;                       // warp stream currently ordered after `stream`
@@ -99,58 +158,59 @@ struct hf_ctx {
 
     // device memory (reference buffers: opticalFlowCalcSDR.cpp:272-280)
     size_t in_bytes = 0, out_bytes = 0, plane_elems = 0;
-    void* ring[3] = {nullptr, nullptr, nullptr};       // m_inputFrameArray, ring[2] = newest (may point at caller memory)
-    void* ring_store[3] = {nullptr, nullptr, nullptr}; // the context's own frame buffers, rotating with the ring
-    uint32_t* pp[3] = {nullptr, nullptr, nullptr};     // phase plane of each ring frame (hf_flow.hip)
+    void* ring[3] = {nullptr, nullptr, nullptr};       // m_inputFrameArray, ring[2] = newest: views of ring_store or of caller memory
+    hfi::DevBuf<void> ring_store[3];                   // the context's own frame buffers, rotating with the ring
+    hfi::DevBuf<uint32_t> pp[3];                       // phase plane of each ring frame (hf_flow.hip)
     bool plane_pending[3] = {false, false, false};     // deferred build (hf_batch_run_period): pp[i] holds only the grid samples so far
     hf::PhaseLayout pl{};
-    void* out_frame = nullptr;                         // m_outputFrameArray
-    void* out_target = nullptr;                        // where warp/copy write (out_frame or caller's)
-    int16_t* tables = nullptr;                         // per-level window offsets (replaces the per-pixel m_offsetArray)
+    hfi::DevBuf<void> out_frame;                       // m_outputFrameArray
+    void* out_target = nullptr;                        // where warp/copy write (out_frame, an output-ring slot or the caller's)
+    hfi::DevBuf<int16_t> tables;                       // per-level window offsets (replaces the per-pixel m_offsetArray); FlowLevel::tx / ty point into it
     size_t tables_bytes = 0;
     std::vector<hf::FlowLevel> levels;                 // level k = window size initial_window >> k
     hf::FlowLevel last_level{};                        // level the last chain ended on (tx == nullptr: no step ran)
-    int16_t* off_view = nullptr;                       // scratch [2][lh][lw] for hf_read_offsets
-    int16_t* blurred[2] = {nullptr, nullptr};          // m_blurredOffsetArray
-    uint32_t* blurred_xy[2] = {nullptr, nullptr};      // the same flow packed x | y << 16 (fast warp path)
-    uint32_t* sadtab = nullptr;                        // SAD tables (hf_flow.hip): [2][sad_nby][sad_nbx][8] u16 pairs; nullptr: HF_FLAG_NO_SAD_REUSE
+    hfi::DevBuf<int16_t> off_view;                     // scratch [2][lh][lw] for hf_read_offsets
+    hfi::DevBuf<int16_t> blurred[2];                   // m_blurredOffsetArray
+    hfi::DevBuf<uint32_t> blurred_xy[2];               // the same flow packed x | y << 16 (fast warp path)
+    hfi::DevBuf<uint32_t> sadtab;                      // SAD tables (hf_flow.hip): [2][sad_nby][sad_nbx][8] u16 pairs; empty: HF_FLAG_NO_SAD_REUSE
     size_t sadtab_bytes = 0;
     int sad_nbx = 0, sad_nby = 0;
     // Content hint of the SAD tables: how many windows of the 32-level chose d = 0 on both axes in the last chains (device counter, published
     // by the chain's last kernel into h_total_delta[1]); below ~30 % of them the tables cost more than they return and the chain runs without
     bool tab_mode = true;                              // the next chain keeps SAD tables
     float still_share = -1.f;                          // smoothed share of such windows (< 0: no chain has reported yet)
-    uint32_t* still_count = nullptr;
-    uint32_t* counters = nullptr;                      // diagnostic counters (hf_debug_counters_enable), device, hf::kCounterWords u32
-    uint32_t* sums = nullptr;                          // [kMaxSteps][n_windows_max][16]
+    hfi::DevBuf<uint32_t> still_count;
+    hfi::DevBuf<uint32_t> counters;                    // diagnostic counters (hf_debug_counters_enable), device, hf::kCounterWords u32
+    hfi::DevBuf<uint32_t> sums;                        // [kMaxSteps][n_windows_max][16]
     size_t sums_bytes = 0;
     size_t sums_stride = 0;                            // elements per step
     uint32_t* d_total_delta = nullptr;                 // device view of h_total_delta (mapped pinned memory)
-    uint32_t* h_total_delta = nullptr;                 // pinned host slot the chain writes m_totalFrameDelta into
-    float* d_probe = nullptr;
-    hf::FrameErrorSlot* error_slots = nullptr;         // hf_frame_error* (hf_metrics.hip): HF_ERROR_SLOTS + 1 result slots, allocated on first use
+    hfi::HostBuf<uint32_t> h_total_delta;              // pinned host slot the chain writes m_totalFrameDelta into
+    hfi::DevBuf<float> d_probe;
+    hfi::DevBuf<hf::FrameErrorSlot> error_slots;       // hf_frame_error* (hf_metrics.hip): HF_ERROR_SLOTS + 1 result slots, allocated on first use
 
-    // asynchronous host I/O (hf_update_frame_async / hf_download_frame_async): side streams, created lazily
+    // asynchronous host I/O (hf_update_frame_async / hf_download_frame_async): side streams, created lazily and all at once (io_init)
     static constexpr int kOutRing = 3;
-    hipStream_t io_in = nullptr, io_out = nullptr;
-    hipEvent_t ev_h2d = nullptr, ev_last_launch = nullptr, ev_out_ready = nullptr;
-    hipEvent_t ev_slot_prep[3] = {nullptr, nullptr, nullptr};   // prep of ring_store[i] finished (rotates with the ring)
-    hipEvent_t ev_d2h[kOutRing] = {nullptr, nullptr, nullptr};
+    hfi::Stream io_in, io_out;
+    hfi::Event ev_h2d, ev_last_launch, ev_out_ready;
+    hfi::Event ev_slot_prep[3];                                  // prep of ring_store[i] finished (rotates with the ring)
+    hfi::Event ev_d2h[kOutRing];
     bool d2h_pending[kOutRing] = {false, false, false};
-    void* out_ring[kOutRing] = {nullptr, nullptr, nullptr};      // [0] == out_frame
+    hfi::DevBuf<void> out_ring[kOutRing];                        // output-ring slots 1 and 2; slot 0 is out_frame and [0] stays empty: out_at()
+    void* out_at(int i) const { return i ? out_ring[i].get() : out_frame.get(); }
     int out_idx = 0;
     bool have_last_launch = false;
     // completion of the asynchronous readbacks, for streaming hosts (hf_wait_download): one event per download, ring of kDlRing
     static constexpr int kDlRing = 64;
-    hipEvent_t ev_dl[kDlRing] = {};
+    hfi::Event ev_dl[kDlRing];
     uint64_t dl_issued = 0;
-    hipEvent_t ev_flow_done = nullptr;                 // behind the last chain of an asynchronous context (hf_wait_flow)
+    hfi::Event ev_flow_done;                           // behind the last chain of an asynchronous context (hf_wait_flow)
     bool flow_done_recorded = false;
 
     // planar frames at the boundary (HF_FLAG_PLANAR_IN / _OUT, hf_planar.hip); every buffer is allocated on first use
-    void* in_stage[3] = {nullptr, nullptr, nullptr};             // planar host frames land here (rotates with ring_store / ev_slot_prep)
-    void* out_stage[kOutRing] = {nullptr, nullptr, nullptr};     // planar frames the readbacks read ([i] paired with out_ring[i])
-    std::vector<void*> period_stage;                             // semi-planar targets of a period's warps where its output side is planar
+    hfi::DevBuf<void> in_stage[3];                               // planar host frames land here (rotates with ring_store / ev_slot_prep)
+    hfi::DevBuf<void> out_stage[kOutRing];                       // planar frames the readbacks read ([i] paired with output-ring slot i)
+    std::vector<hfi::DevBuf<void>> period_stage;                 // semi-planar targets of a period's warps where its output side is planar
                                                                  // (ensure_period_stages: kMaxWarpOutputs at the most, reused chunk by chunk)
     bool planar_in() const { return (cfg.flags & HF_FLAG_PLANAR_IN) != 0; }
     bool planar_out() const { return (cfg.flags & HF_FLAG_PLANAR_OUT) != 0; }
@@ -162,15 +222,15 @@ struct hf_ctx {
     int last_iterations = 0, initial_window = 0;
 
     // timing (reference spans: opticalFlowCalcSDR.cpp:36-41,119-127)
-    hipEvent_t ev_upload = nullptr, ev_flow_end = nullptr, ev_warp_start = nullptr, ev_warp_end = nullptr;
-    hipEvent_t ev_user0 = nullptr, ev_user1 = nullptr;
+    hfi::Event ev_upload, ev_flow_end, ev_warp_start, ev_warp_end;
+    hfi::Event ev_user0, ev_user1;
     bool upload_recorded = false, flow_timing_pending = false, warp_started = false;
 
     ChainGraphs graphs;
 
     // HF_FLAG_PROFILE: event pairs around warp / copy / flow-chain launches
-    struct Span { hipEvent_t b, e; int kind; hipStream_t stream; int frames = 1; };
-    std::vector<hipEvent_t> ev_pool;
+    struct Span { hfi::Event b, e; int kind; hipStream_t stream; int frames = 1; };
+    std::vector<hfi::Event> ev_pool;
     std::vector<Span> spans;
     hf_profile prof{};
     int prof_every[3] = {1, 1, 1};   // sampling interval per span kind (warp, copy, flow chain)
@@ -185,8 +245,8 @@ struct hf_ctx {
 struct hf_timeline final : hf::LaunchObserver {
     struct Rec { const char* name; hipEvent_t b, e; int period; };
     std::vector<Rec> recs;
-    std::vector<hipEvent_t> events;      // 2 per record, created when the timeline is switched on
-    hipEvent_t anchor = nullptr;         // recorded when it is switched on: the records are read against it, it against the process's reference
+    std::vector<hfi::Event> events;      // 2 per record, created when the timeline is switched on
+    hfi::Event anchor;                   // recorded when it is switched on: the records are read against it, it against the process's reference
     double anchor_ms = 0.0;
     size_t capacity = 0;
     int skip = 0;                        // hf_batch_run_period calls still to pass unobserved before the recording starts
@@ -195,7 +255,7 @@ struct hf_timeline final : hf::LaunchObserver {
     uint64_t dropped = 0;                // launches issued while on but out of records (cannot happen: it switches itself off when full)
     bool next(const char* name, hipEvent_t* s, hipEvent_t* e) override {
         if (recs.size() >= capacity) { dropped++; return false; }
-        *s = events[2 * recs.size()]; *e = events[2 * recs.size() + 1];
+        *s = events[2 * recs.size()].get(); *e = events[2 * recs.size() + 1].get();
         recs.push_back(Rec{name, *s, *e, period});
         return true;
     }
@@ -205,10 +265,10 @@ struct hf_timeline final : hf::LaunchObserver {
 struct hf_batch {
     hf_timeline tl;
     std::vector<hf_ctx*> members;
-    std::vector<hipStream_t> own_streams;   // the members' own streams, restored by hf_batch_destroy
+    std::vector<hipStream_t> own_streams;   // views of the members' own streams, restored by hf_batch_destroy
     std::vector<hipStream_t> own_warp_streams;
-    std::vector<hipStream_t> warp_streams;  // HF_FLAG_DUAL_STREAM members: shared streams their warps are issued on
-    hipStream_t stream = nullptr;           // the batch's own (highest-priority) stream, shared by all members while the batch exists
+    std::vector<hfi::Stream> warp_streams;  // HF_FLAG_DUAL_STREAM members: shared streams their warps are issued on
+    hfi::Stream stream;                     // the batch's own (highest-priority) stream, shared by all members while the batch exists
     ChainGraphs graphs;
     bool defer_planes = false;              // hf_batch_run_period: grid samples at update, full plane of frame N-1 from the warp launch
     bool auto_deferred = false;             // ... and hf_batch_run_period_auto too: the leader's HF_FLAG_BATCH_AUTO_DEFERRED on a batch that defers
@@ -224,9 +284,10 @@ struct hf_batch {
         uint64_t written = 0, read = 0;     // records appended / handed out so far (slot = index % kSceneRing)
     };
     std::vector<SceneMember> scene;
-    hf::SceneState* scene_states = nullptr; // device [kMaxFlowBatch]
-    int32_t* scene_kinds = nullptr;         // device [kMaxFlowBatch]: 1 warp / 0 copy of the period in flight
-    hf::SceneRecord* scene_records = nullptr, *scene_records_dev = nullptr;   // mapped host memory [kMaxFlowBatch][kSceneRing] and its device view
+    hfi::DevBuf<hf::SceneState> scene_states;   // device [kMaxFlowBatch]
+    hfi::DevBuf<int32_t> scene_kinds;           // device [kMaxFlowBatch]: 1 warp / 0 copy of the period in flight
+    hfi::HostBuf<hf::SceneRecord> scene_records;   // mapped host memory [kMaxFlowBatch][kSceneRing] ...
+    hf::SceneRecord* scene_records_dev = nullptr;  // ... and its device view
     std::string err;
 };
 
@@ -238,7 +299,7 @@ int set_device(hf_ctx* c);
 int initial_window(int lw, int lh);
 int ilog2(int v);
 int effective_iterations(const hf_ctx* c);
-hipEvent_t pool_event(hf_ctx* c);
+Event pool_event(hf_ctx* c);
 int span_begin(hf_ctx* c, int kind, hipStream_t stream = nullptr);
 int span_open(hf_ctx* c, int kind);
 void span_end(hf_ctx* c, int idx);

@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -23,11 +24,14 @@
 #include "../../include/config.h"
 #include "../../include/hopperflow.h"
 
+struct FreePinned { void operator()(void* p) const { hf_host_free_pinned(p); } };
+using PinnedFrame = std::unique_ptr<void, FreePinned>;   // a frame from hf_host_malloc_pinned that this driver owns
+
 struct hf_hostio {
     hf_ctx* ctx = nullptr;
     hf_hostio_config cfg{};
     hf_stats st{};
-    std::vector<void*> ins, outs;
+    std::vector<PinnedFrame> ins, outs;
     uint64_t bytes_in = 0, bytes_out = 0;
     std::string err;
 };
@@ -124,7 +128,7 @@ int hf_hostio_create(hf_ctx* ctx, const hf_hostio_config* cfg, hf_hostio** out) 
         void* p = nullptr;
         const size_t bytes = i < h->cfg.in_ring ? (size_t)h->st.input_frame_bytes : (size_t)h->st.output_frame_bytes;
         if (int rc = hf_host_malloc_pinned(bytes, &p)) { hf_hostio_destroy(h); return hio_fail(nullptr, rc, "hf_hostio_create: pinned allocation failed"); }
-        (i < h->cfg.in_ring ? h->ins : h->outs).push_back(p);
+        (i < h->cfg.in_ring ? h->ins : h->outs).push_back(PinnedFrame(p));
     }
     *out = h;
     return HF_OK;
@@ -132,9 +136,7 @@ int hf_hostio_create(hf_ctx* ctx, const hf_hostio_config* cfg, hf_hostio** out) 
 
 void hf_hostio_destroy(hf_hostio* h) {
     if (!h) return;
-    if (h->ctx) hf_sync(h->ctx);
-    for (void* p : h->ins) hf_host_free_pinned(p);
-    for (void* p : h->outs) hf_host_free_pinned(p);
+    if (h->ctx) hf_sync(h->ctx);   // no transfer into or out of the pinned frames is in flight when they go
     delete h;
 }
 
@@ -175,13 +177,13 @@ int hf_hostio_run(hf_hostio* h, const hf_timeline_chunk* chunk, const int32_t* n
     auto drain = [&](int64_t upto) -> int {
         while (drained < upto) {
             if (int rc = hf_wait_download(c, base + (uint64_t)drained)) return hio_fail(h, rc, std::string("hf_wait_download failed: ") + hf_last_error(c));
-            if (int rc = sink(user, drained, h->outs[(size_t)(drained % R)], kind_of[(size_t)drained])) return hio_fail(h, HF_ERR_STATE, "hf_hostio_run: sink returned " + std::to_string(rc));
+            if (int rc = sink(user, drained, h->outs[(size_t)(drained % R)].get(), kind_of[(size_t)drained])) return hio_fail(h, HF_ERR_STATE, "hf_hostio_run: sink returned " + std::to_string(rc));
             drained++;
         }
         return HF_OK;
     };
     for (int64_t k = chunk->first_frame; k < chunk->first_frame + chunk->n_frames; k++) {
-        void* slot = h->ins[(size_t)((k - chunk->first_frame) % (int64_t)h->ins.size())];
+        void* slot = h->ins[(size_t)((k - chunk->first_frame) % (int64_t)h->ins.size())].get();
         // (the upload that last used this slot finished before an earlier hf_wait_flow / hf_sync)
         if (int rc = fill(user, k, slot)) return hio_fail(h, HF_ERR_STATE, "hf_hostio_run: fill returned " + std::to_string(rc));
         HIO(hf_update_frame_async(c, slot));
@@ -209,7 +211,7 @@ int hf_hostio_run(hf_hostio* h, const hf_timeline_chunk* chunk, const int32_t* n
                 kind_of.push_back(0);
             }
             if (int rc = drain(issued - R + 1)) return rc;   // the slot about to be overwritten must have gone to the sink
-            HIO(hf_download_frame_async(c, h->outs[(size_t)(issued % R)]));
+            HIO(hf_download_frame_async(c, h->outs[(size_t)(issued % R)].get()));
             issued++;
             h->bytes_out += h->st.output_frame_bytes;
         }

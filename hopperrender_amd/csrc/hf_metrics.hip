@@ -274,9 +274,9 @@ static int enqueue_errors(hf_ctx* c, const char* who, int n, const void* const* 
     if (stride_a < c->g.W || stride_b < c->g.W) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: strides %d / %d below the frame width %d", who, stride_a, stride_b, c->g.W);
     if (planar && ((stride_a | stride_b) & 1)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: planar frames need even strides (%d / %d)", who, stride_a, stride_b);
     if (int rc = set_device(c)) return rc;
-    if (!c->error_slots) HF_HIP(c, hipMalloc((void**)&c->error_slots, (size_t)(HF_ERROR_SLOTS + 1) * sizeof(hf::FrameErrorSlot)));
+    if (!c->error_slots) HF_HIP(c, alloc_device(c->error_slots, (size_t)(HF_ERROR_SLOTS + 1) * sizeof(hf::FrameErrorSlot)));
     if (int rc = leave_warp_stream(c)) return rc;
-    hf::FrameErrorSlot* slots = c->error_slots + first_slot;
+    hf::FrameErrorSlot* slots = c->error_slots.get() + first_slot;
     HF_HIP(c, hipMemsetAsync(slots, 0, (size_t)n * sizeof(hf::FrameErrorSlot), c->stream));
     if (!hf::launch_frame_errors(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, n, a, b, slots, c->stream))
         return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
@@ -291,7 +291,7 @@ static int read_errors(hf_ctx* c, int first_slot, int n, int max_slot, struct hf
     if (!c->error_slots) return fail(c, HF_ERR_STATE, "hf_frame_error_read: nothing was enqueued");
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(out, c->error_slots + first_slot, (size_t)n * sizeof(struct hf_frame_error), hipMemcpyDeviceToHost, c->stream));
+    HF_HIP(c, hipMemcpyAsync(out, c->error_slots.get() + first_slot, (size_t)n * sizeof(struct hf_frame_error), hipMemcpyDeviceToHost, c->stream));
     return sync_ctx(c);
 }
 

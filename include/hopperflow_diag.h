@@ -83,6 +83,20 @@ int hf_clock_probe(int device_index, int duration_us, double* shader_mhz);
  * `repeats` passes; read + write bytes per second, GB/s): the yardstick a bandwidth-bound pipeline should be held against on THIS box. */
 int hf_hbm_copy_probe(int device_index, size_t bytes, int repeats, double* read_plus_write_GBps);
 
+/* How many resources the library holds for itself in this process right now, per kind: what a leak test compares before and after (exact
+ * counts, where the device's free memory moves with everybody else's work and does not see events, streams or graph executables at all).
+ * Counted where they are created and released, nowhere on a period's steady-state path.  Not counted: memory handed to the caller by
+ * hf_device_malloc / hf_host_malloc_pinned, which is the caller's, and the timeline's one reference event per device, which lives as long
+ * as the process.  Takes no context, needs no device, does not synchronise; a null argument is HF_ERR_INVALID_ARGUMENT. */
+typedef struct hf_live_resources {
+    int64_t device_buffers;
+    int64_t pinned_buffers;   /* pinned or mapped host memory */
+    int64_t streams;
+    int64_t events;
+    int64_t graph_execs;      /* instantiated graphs of the refinement chain */
+} hf_live_resources;
+int hf_debug_live_resources(hf_live_resources* out);
+
 /* ---- measurement: HIP events on ctx's own stream (torch events cannot see this stream) ---- */
 int hf_timer_begin(hf_ctx* ctx);
 int hf_timer_end(hf_ctx* ctx, float* elapsed_ms); /* synchronises on the end event */

@@ -1,4 +1,5 @@
-"""Device-memory leak check: contexts, batches (single- and dual-stream members), caller buffers created and destroyed in a loop."""
+"""Leak check: contexts, batches (single- and dual-stream members), caller buffers created and destroyed in a loop.  Prints the library's
+own count of what it holds (hf_debug_live_resources: exact) and the device's free memory (which moves with everybody else's work)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,7 +21,9 @@ def cycle(n):
         for c in cs: c.close()
         for o in outs: o.free()
 cycle(3)
-torch.cuda.synchronize(); free0, total = torch.cuda.mem_get_info()
+torch.cuda.synchronize(); free0, total = torch.cuda.mem_get_info(); live0 = capi.live_resources()
 cycle(40)
-torch.cuda.synchronize(); free1, _ = torch.cuda.mem_get_info()
+torch.cuda.synchronize(); free1, _ = torch.cuda.mem_get_info(); live1 = capi.live_resources()
+print("live before %s" % live0)
+print("live after  %s" % live1)
 print("free before %.1f MB, after %.1f MB, delta %.1f MB" % (free0 / 1e6, free1 / 1e6, (free0 - free1) / 1e6))
