@@ -24,6 +24,10 @@ HIP_CASES = [   # hdr, H, W, si, so, R, delta, nb, seed, max_res
     (1, 2160, 3840, 0, 0, 16, 8, 6, 505, 270),
     (0, 568, 1388, 0, 0, 12, 3, 4, 506, 1000),      # maxCalcRes above the default: 1388-wide grid, windows > 32 at neighbour-term levels
     (1, 540, 960, 0, 0, 9, 8, 6, 507, 540),         # rs = 0 at qHD
+    # a kind of tests/chain_content.py in place of the seed: exact ties between a window's best candidates at every step class
+    # (tests/test_chain_tie_model.py), so the record pins the reference's own choice among equal sums, the first
+    (0, 256, 480, 0, 0, 16, 0, 0, "tie-d0", 270),
+    (1, 540, 960, 0, 0, 16, 3, 2, "tie-d3", 270),
 ]
 HIP_TVALS = [0.0, 0.1998, 0.3996, 0.5994, 0.999]
 TINY_CASES = [(0, 4, 4), (1, 4, 4), (0, 6, 10)]     # hdr, H, W
@@ -36,8 +40,13 @@ def sha(a):
 
 
 def hip_case(hdr, H, W, si, so, R, delta, nb, seed, max_res):
-    sc = synth.Scene(H, W, bool(hdr), seed, in_stride=si)
-    f = [sc.frame(k) for k in range(4)]
+    if isinstance(seed, str):
+        import chain_content
+        rs = next(r for r in range(16) if (H >> r) <= max_res)
+        f = chain_content.frames(seed, H, W, bool(hdr), chain_content.kind_seed(seed), 4, si, rs)
+    else:
+        sc = synth.Scene(H, W, bool(hdr), seed, in_stride=si)
+        f = [sc.frame(k) for k in range(4)]
 
     def script(s):
         s.radius(R)
@@ -45,6 +54,8 @@ def hip_case(hdr, H, W, si, so, R, delta, nb, seed, max_res):
             s.update(x)
         s.calc(); s.stats(); s.dump_offsets("off"); s.dump_blurred(1, "blur")
         s.update(f[3]); s.calc(); s.stats()
+        if isinstance(seed, str):
+            s.dump_offsets("off2")
         for m in (0, 1, 2):
             for t in HIP_TVALS:
                 s.warp(t, m); s.download(f"w{m}_{t}")

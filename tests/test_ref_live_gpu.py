@@ -27,6 +27,8 @@ def test_hip_matches_live_reference(native_lib, hdr, H, W, si, so, R, delta, nb,
     assert ref.same("blur", c.readBlurredFlow(1))
     c.updateFrame(f[3]); c.calculateOpticalFlow()
     assert c.m_totalFrameDelta == js[1]["total_frame_delta"]
+    if "off2" in ref.outputs:          # the tie cases: the second pair's offsets too
+        assert ref.same("off2", c.readOffsets())
     for m in (0, 1, 2):
         for t in tvals:
             c.warpFrames(t, m)
