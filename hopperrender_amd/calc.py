@@ -197,6 +197,42 @@ class OpticalFlowCalc:
                                             int(stride_b) or self.m_frameWidth, 1 if planar else 0, C.byref(e)), self._ctx)
         return self._frame_error_dict(e)
 
+    # ---- windowed SSIM on the device (hf_frame_ssim*) ----
+    @staticmethod
+    def _frame_ssim_dict(e):
+        """struct hf_frame_ssim as {'Y': {...}, 'U': {...}, 'V': {...}}: the plain ints sum_loss_q32, max_loss_q32, count and the floats
+        ssim = 1 - sum_loss_q32 / 2^32 / count (mean) and min_ssim = 1 - max_loss_q32 / 2^32 (worst window); None where count == 0"""
+        out = {}
+        for i, p in enumerate("YUV"):
+            s, m, n = int(e.sum_loss_q32[i]), int(e.max_loss_q32[i]), int(e.count[i])
+            out[p] = {"sum_loss_q32": s, "max_loss_q32": m, "count": n, "ssim": 1.0 - s / 4294967296.0 / n if n else None,
+                      "min_ssim": 1.0 - m / 4294967296.0 if n else None}
+        return out
+
+    def frameSsimEnqueue(self, a_ptrs, b_ptrs, first_slot=0, stride_a=0, stride_b=0, planar=False, peak=0):
+        """hf_frame_ssim_enqueue: score device frames a_ptrs[i] against b_ptrs[i] into SSIM slot first_slot + i, behind everything this
+        context has enqueued; only enqueues.  Strides in elements, 0 = the frame width; peak 0 = the format's own."""
+        n = len(a_ptrs)
+        if len(b_ptrs) != n:
+            raise ValueError("frameSsimEnqueue: as many b frames as a frames")
+        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
+        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
+        capi.check(self._lib.hf_frame_ssim_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
+                                                   1 if planar else 0, int(peak), int(first_slot)), self._ctx)
+
+    def frameSsimRead(self, first_slot, n):
+        """hf_frame_ssim_read: wait for this context's work and return SSIM slots [first_slot, first_slot + n) as dicts."""
+        out = (capi.HfFrameSsim * max(int(n), 1))()
+        capi.check(self._lib.hf_frame_ssim_read(self._ctx, int(first_slot), int(n), out), self._ctx)
+        return [self._frame_ssim_dict(e) for e in out[:n]]
+
+    def frameSsim(self, a_ptr, b_ptr, stride_a=0, stride_b=0, planar=False, peak=0):
+        """hf_frame_ssim: one pair, blocking."""
+        e = capi.HfFrameSsim()
+        capi.check(self._lib.hf_frame_ssim(self._ctx, C.c_void_p(a_ptr or 0), C.c_void_p(b_ptr or 0), int(stride_a) or self.m_frameWidth,
+                                           int(stride_b) or self.m_frameWidth, 1 if planar else 0, int(peak), C.byref(e)), self._ctx)
+        return self._frame_ssim_dict(e)
+
     def setOutputBuffer(self, dev_ptr):
         capi.check(self._lib.hf_set_output_buffer(self._ctx, C.c_void_p(dev_ptr or 0)), self._ctx)
 

@@ -188,6 +188,7 @@ struct hf_ctx {
     hfi::HostBuf<uint32_t> h_total_delta;              // pinned host slot the chain writes m_totalFrameDelta into
     hfi::DevBuf<float> d_probe;
     hfi::DevBuf<hf::FrameErrorSlot> error_slots;       // hf_frame_error* (hf_metrics.hip): HF_ERROR_SLOTS + 1 result slots, allocated on first use
+    hfi::DevBuf<hf::FrameSsimSlot> ssim_slots;         // hf_frame_ssim* (hf_metrics.hip): HF_SSIM_SLOTS + 1 slots of their own, allocated on first use
 
     // asynchronous host I/O (hf_update_frame_async / hf_download_frame_async): side streams, created lazily and all at once (io_init)
     static constexpr int kOutRing = 3;

@@ -200,6 +200,14 @@ struct FrameErrorSlot {
 constexpr int kMaxErrorPairs = 192;
 bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
                          FrameErrorSlot* slots, hipStream_t stream);
+// Windowed SSIM (hf_metrics.hip; hf_frame_ssim*): the same pairs, strides and layouts as launch_frame_errors; per plane the summed and the
+// largest loss 2^32 - round(ssim 2^32) over the 8 x 8 windows at stride 4 and their number, with the integer constants c1, c2 of the peak
+// (include/hopperflow.h has the definition).  The layout of hf_frame_ssim; slots zeroed by the caller on the same stream.
+struct FrameSsimSlot {
+    uint64_t sum_loss_q32[3], max_loss_q32[3], count[3];   // index 0 Y, 1 U, 2 V
+};
+bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int n, const void* const* a,
+                       const void* const* b, FrameSsimSlot* slots, hipStream_t stream);
 bool dbg_bounds_read_metrics(unsigned out[5], bool reset);
 // Scene-cut copy periods of a batch, decided on the device (hf_scene.hip; hf_batch_run_period_auto).  One record per member and period:
 // the layout of hf_scene_record (include/hopperflow.h).

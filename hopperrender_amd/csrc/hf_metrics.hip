@@ -17,6 +17,8 @@
 // Per lane: 64-bit sums over its items (two 16-bit elements already overflow 32 bits of squares); then the wave (shuffles), the
 // workgroup's waves (LDS), and ONE atomicAdd / atomicMax per quantity, plane and workgroup into the pair's slot, which a hipMemsetAsync
 // ahead of the launch zeroed.  Grid-stride over at most ~2048 workgroups per launch, one at least per pair.
+//
+// Further down: the windowed SSIM of the same pairs (hf_frame_ssim*), with its own kernel, launcher and slots.
 #include <type_traits>
 
 #include "hf_ctx.h"
@@ -195,6 +197,321 @@ __global__ void __launch_bounds__(kErrBlock) frame_error_kernel(const ErrorArgs 
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---- Windowed SSIM (hf_frame_ssim*; the definition is in include/hopperflow.h) ----
+// Per plane: integer sums s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b over the 4 x 4 blocks of the plane; a window is
+// 2 x 2 blocks; its score goes through five double operations and comes back as the integer loss 2^32 - round(ssim 2^32).  The same
+// pointer table, layouts and pitches as the error sums above, and the same work item: 16 bytes of a row on each side -- here of four
+// rows, a UNIT = 4 (8 bit) or 2 (16 bit) blocks; in an interleaved UV row half as many blocks of U and of V each.
+// A workgroup takes TILES of kSsimUnitsX units by kSsimRows block rows, the last unit and the last block row of which are halo (read
+// again by the neighbouring tile, mostly from L2: 32 / 31 x 16 / 15 = 1.10 of the frame); every lane has two (unit, block row) positions:
+//     0. the four 16-byte loads per side of each position are issued (where the launcher found every frame of the launch aligned and
+//        the unit lies whole inside the row) -- for the tile AFTER the current one, so that they fly while step 2 computes;
+//     1. the blocks of the two units are summed (from those rows; element by element otherwise -- the same integers) and left in LDS;
+//     2. after a barrier: per position the column sums of the unit's blocks and of the first block of the unit to the right over this
+//        block row and the next, and from two neighbouring column sums each window.
+// Tiles are numbered through the planes of a frame (luma, then chroma); a workgroup strides over them, keeps loss sum, largest loss and
+// window count per plane in registers, and ends like the error kernel: wave shuffles, LDS, one atomic per quantity and plane.
+constexpr int kSsimBlock = 256;
+constexpr int kSsimUnitsX = 32, kSsimRows = 16;     // a tile, halo included
+constexpr int kSsimItems = kSsimUnitsX * kSsimRows;
+
+static_assert(sizeof(FrameSsimSlot) == sizeof(struct hf_frame_ssim) && offsetof(FrameSsimSlot, max_loss_q32) == offsetof(struct hf_frame_ssim, max_loss_q32) &&
+              offsetof(FrameSsimSlot, count) == offsetof(struct hf_frame_ssim, count), "FrameSsimSlot is hf_frame_ssim");
+
+struct SsimPlane {
+    uint32_t bw, bh;                 // blocks across / down, per channel
+    uint32_t w_row;                  // elements of a row that may be read (interleaved UV: of both channels)
+    uint32_t pitch_a, pitch_b;       // elements
+    uint32_t tiles_x, tile_first;    // tiles across; number of the plane's first tile within the frame
+    int vec;                         // every row of the plane starts 16-byte aligned in every frame of the launch
+    size_t base_a, base_b;           // first row, elements
+};
+struct SsimShape {
+    SsimPlane pl[3];                 // luma; interleaved UV, or U and V
+    uint32_t tiles;
+    size_t elems_a, elems_b;         // extent of a frame of side a / b (debug-bounds)
+    long long c1, c2;
+};
+struct SsimArgs {
+    SsimShape sh;
+    int n;
+    FrameSsimSlot* slots;            // slot of pair 0
+    const void* a[kMaxErrorPairs];
+    const void* b[kMaxErrorPairs];
+};
+static_assert(sizeof(SsimArgs) <= 4096, "kernel arguments: 4 KB");
+
+// the sums of a block, of a column of two, of a window: 64 8-bit elements fit 32 bits everywhere, one 16-bit product already fills them
+template <typename T>
+struct SsimBlk {
+    using Q = typename std::conditional<sizeof(T) == 1, uint32_t, uint64_t>::type;
+    uint32_t s1, s2;
+    Q ss, s12;
+    __device__ __forceinline__ void add1(uint32_t a, uint32_t b) { s1 += a; s2 += b; ss += (Q)a * a + (Q)b * b; s12 += (Q)a * b; }
+    __device__ __forceinline__ SsimBlk operator+(const SsimBlk& o) const { return SsimBlk{s1 + o.s1, s2 + o.s2, ss + o.ss, s12 + o.s12}; }
+};
+
+// a block summed from whole words of its rows (bytes or halves masked away are zero on both sides and add nothing), full-rate dot
+// products only.  8 bit: four elements per word, five v_dot4_u32_u8.  16 bit: two elements per word; a 64-bit multiply-add per product
+// runs at a quarter of the rate, so the products are taken byte-wise, a = 256 ah + al:  a b = 65536 ah bh + 256 (ah bl + al bh) + al bl.
+// Over the bytes of a word, dot4(a, b) = sum (al bl + ah bh), dot4(a & 0x00FF00FF, b) = sum al bl, and against b with the bytes of each
+// half swapped, sum (al bh + ah bl); the three 32-bit sums of a block's 16 elements (each below 2^23) go together once, in finish().
+template <typename T>
+struct SsimWide;
+template <>
+struct SsimWide<uint8_t> {
+    SsimBlk<uint8_t> b = {0, 0, 0, 0};
+    __device__ __forceinline__ void add(uint32_t x, uint32_t y) {
+        b.s1 = __builtin_amdgcn_udot4(x, 0x01010101u, b.s1, false); b.s2 = __builtin_amdgcn_udot4(y, 0x01010101u, b.s2, false);
+        b.ss = __builtin_amdgcn_udot4(x, x, __builtin_amdgcn_udot4(y, y, b.ss, false), false);
+        b.s12 = __builtin_amdgcn_udot4(x, y, b.s12, false);
+    }
+    __device__ __forceinline__ SsimBlk<uint8_t> finish() const { return b; }
+};
+template <>
+struct SsimWide<uint16_t> {
+    uint32_t s1 = 0, s2 = 0;
+    uint32_t q_all = 0, q_lo = 0, q_x = 0;   // of a^2 + b^2: sum (l^2 + h^2), sum l^2, sum 2 l h
+    uint32_t p_all = 0, p_lo = 0, p_x = 0;   // of a b: sum (al bl + ah bh), sum al bl, sum (al bh + ah bl)
+    __device__ __forceinline__ void add(uint32_t x, uint32_t y) {
+        const u16x2 one = {1, 1};
+        s1 = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, x), one, s1, false); s2 = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, y), one, s2, false);
+        const uint32_t xs = __builtin_amdgcn_perm(x, x, 0x02030001u), ys = __builtin_amdgcn_perm(y, y, 0x02030001u);   // bytes of each half swapped
+        const uint32_t xl = x & 0x00FF00FFu, yl = y & 0x00FF00FFu;
+        q_all = __builtin_amdgcn_udot4(x, x, __builtin_amdgcn_udot4(y, y, q_all, false), false);
+        q_lo = __builtin_amdgcn_udot4(xl, x, __builtin_amdgcn_udot4(yl, y, q_lo, false), false);
+        q_x = __builtin_amdgcn_udot4(x, xs, __builtin_amdgcn_udot4(y, ys, q_x, false), false);
+        p_all = __builtin_amdgcn_udot4(x, y, p_all, false); p_lo = __builtin_amdgcn_udot4(xl, y, p_lo, false); p_x = __builtin_amdgcn_udot4(x, ys, p_x, false);
+    }
+    __device__ __forceinline__ SsimBlk<uint16_t> finish() const {
+        return SsimBlk<uint16_t>{s1, s2, ((uint64_t)(q_all - q_lo) << 16) + ((uint64_t)q_x << 8) + q_lo, ((uint64_t)(p_all - p_lo) << 16) + ((uint64_t)p_x << 8) + p_lo};
+    }
+};
+
+struct SsimAcc {         // one plane's windows of a wave, a workgroup
+    unsigned long long sum, mx;
+    uint32_t cnt;
+};
+// ... and of a lane: losses are integers up to 2^33, and a lane sees fewer than 2^20 windows of a plane in a launch (the launcher holds it
+// to that), so doubles carry their sum and their maximum exactly -- an add and a max per window where 64-bit integers take a conversion,
+// two additions with carry and a three-instruction maximum
+struct SsimLane {
+    double sum, mx;
+    uint32_t cnt;
+};
+constexpr uint32_t kSsimMaxTilesPerWorkgroup = 1u << 17;   // x 8 windows of a plane per lane and tile
+
+// 2^32 - round(ssim 2^32) of a window's sums, an integer in a double.  Every term is below 2^53 in magnitude, so its conversion is exact;
+// two multiplications, one (correctly rounded) division; the scaling is exact, v_rndne_f64 rounds to nearest even, the difference is exact.
+template <typename T>
+__device__ __forceinline__ double ssim_loss(const SsimBlk<T>& w, long long c1, long long c2) {
+    if constexpr (sizeof(T) == 1) {
+        // 8 bit: S1, S2 <= 64 * 255, so every term fits 32 bits (2 S1 S2, S1^2 + S2^2, 64 SS <= 2^29; c2 < 2^18) -- the same integers
+        // as below through a fraction of the instructions, and one v_cvt_f64_i32 each
+        const uint32_t p12 = w.s1 * w.s2, sq = w.s1 * w.s1 + w.s2 * w.s2;
+        const int32_t vars = (int32_t)(64u * w.ss - sq), covar = (int32_t)(64u * w.s12) - (int32_t)p12;
+        const int32_t A = (int32_t)(2u * p12) + (int32_t)c1, B = 2 * covar + (int32_t)c2, C = (int32_t)sq + (int32_t)c1, D = vars + (int32_t)c2;
+        const double num = (double)A * (double)B, den = (double)C * (double)D;
+        const double ssim = num / den;
+        return 4294967296.0 - rint(ssim * 4294967296.0);
+    }
+    const long long S1 = w.s1, S2 = w.s2, SS = (long long)w.ss, S12 = (long long)w.s12;
+    const long long vars = 64 * SS - S1 * S1 - S2 * S2, covar = 64 * S12 - S1 * S2;
+    const long long A = 2 * S1 * S2 + c1, B = 2 * covar + c2, C = S1 * S1 + S2 * S2 + c1, D = vars + c2;
+    const double num = (double)A * (double)B, den = (double)C * (double)D;
+    const double ssim = num / den;
+    return 4294967296.0 - rint(ssim * 4294967296.0);
+}
+
+// 16 bytes of a unit's row on either side into the unit's blocks w[channel * BPU + block]
+template <typename T, int CH>
+__device__ __forceinline__ void ssim_add_row(SsimWide<T>* w, const uint4& a, const uint4& b) {
+    if (sizeof(T) == 1) {
+        if (CH == 1) { w[0].add(a.x, b.x); w[1].add(a.y, b.y); w[2].add(a.z, b.z); w[3].add(a.w, b.w); }
+        else {   // U V U V: even bytes U (blocks 0, 1), odd bytes V (blocks 2, 3)
+            constexpr uint32_t m = 0x00FF00FFu;
+            w[0].add(a.x & m, b.x & m); w[0].add(a.y & m, b.y & m); w[1].add(a.z & m, b.z & m); w[1].add(a.w & m, b.w & m);
+            w[2].add((a.x >> 8) & m, (b.x >> 8) & m); w[2].add((a.y >> 8) & m, (b.y >> 8) & m);
+            w[3].add((a.z >> 8) & m, (b.z >> 8) & m); w[3].add((a.w >> 8) & m, (b.w >> 8) & m);
+        }
+    } else {
+        if (CH == 1) { w[0].add(a.x, b.x); w[0].add(a.y, b.y); w[1].add(a.z, b.z); w[1].add(a.w, b.w); }
+        else {   // U V: the low halves of two words are two U elements (block 0), the high halves two V elements (block 1); v_perm_b32
+            constexpr uint32_t lo = 0x05040100u, hi = 0x07060302u;
+            w[0].add(__builtin_amdgcn_perm(a.y, a.x, lo), __builtin_amdgcn_perm(b.y, b.x, lo));
+            w[0].add(__builtin_amdgcn_perm(a.w, a.z, lo), __builtin_amdgcn_perm(b.w, b.z, lo));
+            w[1].add(__builtin_amdgcn_perm(a.y, a.x, hi), __builtin_amdgcn_perm(b.y, b.x, hi));
+            w[1].add(__builtin_amdgcn_perm(a.w, a.z, hi), __builtin_amdgcn_perm(b.w, b.z, hi));
+        }
+    }
+}
+
+// where tile t of a frame lies: plane (0 luma; 1 interleaved UV or U; 2 V) and position
+struct SsimTileAt {
+    uint32_t pl, tx, ty;
+};
+template <bool PLANAR>
+__device__ __forceinline__ SsimTileAt ssim_locate(const SsimShape& s, uint32_t t) {
+    const uint32_t pl = t < s.pl[1].tile_first ? 0u : (!PLANAR || t < s.pl[2].tile_first) ? 1u : 2u;
+    const uint32_t l = t - s.pl[pl].tile_first, ty = l / s.pl[pl].tiles_x;
+    return SsimTileAt{pl, l - ty * s.pl[pl].tiles_x, ty};
+}
+
+// a lane's two (unit, block row) positions of a tile
+constexpr int kSsimPerLane = kSsimItems / kSsimBlock;
+struct SsimRows {        // the 16-byte loads of a tile still in flight: [position][row] of either side
+    uint4 a[kSsimPerLane][4], b[kSsimPerLane][4];
+};
+template <typename T>
+__device__ __forceinline__ bool ssim_wide(const SsimPlane& p, uint32_t u, uint32_t j) {   // unit u of block row j: one 16-byte load per row and side
+    constexpr uint32_t EL = 16 / sizeof(T);
+    return p.vec && j < p.bh && u * EL + EL <= p.w_row;
+}
+
+// step 0 of a tile: issue its wide loads.  Called for the NEXT tile ahead of the windows of the current one, which hide their latency.
+template <typename T>
+__device__ __forceinline__ void ssim_fetch(const T* __restrict__ fa, const T* __restrict__ fb, const SsimShape& s, const SsimPlane& p,
+                                           const SsimTileAt& at, SsimRows& rows) {
+    constexpr uint32_t EL = 16 / sizeof(T);
+    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t it = threadIdx.x + n * kSsimBlock, u = u0 + it % kSsimUnitsX, j = j0 + it / kSsimUnitsX;
+        if (!ssim_wide<T>(p, u, j)) continue;
+#pragma unroll
+        for (uint32_t r = 0; r < 4; r++) {
+            const size_t ia = p.base_a + (size_t)(4u * j + r) * p.pitch_a + u * EL, ib = p.base_b + (size_t)(4u * j + r) * p.pitch_b + u * EL;
+            HF_DBG_CHECK(ia + EL <= s.elems_a && ib + EL <= s.elems_b, 255);
+            rows.a[n][r] = *reinterpret_cast<const uint4*>(fa + ia); rows.b[n][r] = *reinterpret_cast<const uint4*>(fb + ib);
+        }
+    }
+}
+
+// step 1: the block sums of the tile into LDS, from the rows fetched or -- unaligned frames, the ragged end of a row -- element by
+// element.  CH = 2: an interleaved UV plane.
+template <typename T, int CH>
+__device__ __forceinline__ void ssim_sums(const T* __restrict__ fa, const T* __restrict__ fb, const SsimShape& s, const SsimPlane& p,
+                                          const SsimTileAt& at, const SsimRows& rows, SsimBlk<T> (*lds)[4 / sizeof(T)][kSsimUnitsX]) {
+    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
+    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t it = threadIdx.x + n * kSsimBlock, lu = it % kSsimUnitsX, lr = it / kSsimUnitsX, u = u0 + lu, j = j0 + lr;
+        if (j >= p.bh || u * BPU >= p.bw) continue;
+        SsimBlk<T> blk[NB] = {};
+        if (ssim_wide<T>(p, u, j)) {
+            SsimWide<T> w[NB];
+#pragma unroll
+            for (uint32_t r = 0; r < 4; r++) ssim_add_row<T, CH>(w, rows.a[n][r], rows.b[n][r]);
+#pragma unroll
+            for (uint32_t k = 0; k < NB; k++) blk[k] = w[k].finish();
+        } else {
+            const size_t oa = p.base_a + (size_t)(4u * j) * p.pitch_a, ob = p.base_b + (size_t)(4u * j) * p.pitch_b;
+#pragma unroll
+            for (uint32_t c = 0; c < (uint32_t)CH; c++)
+#pragma unroll
+                for (uint32_t k = 0; k < BPU; k++) {
+                    const uint32_t i = u * BPU + k;
+                    if (i >= p.bw) continue;   // (a unit past the last whole block of the row: nothing of it is read)
+                    for (uint32_t r = 0; r < 4; r++)
+                        for (uint32_t e = 0; e < 4; e++) {
+                            const uint32_t x = (4u * i + e) * CH + c;
+                            const size_t ia = oa + (size_t)r * p.pitch_a + x, ib = ob + (size_t)r * p.pitch_b + x;
+                            HF_DBG_CHECK(x < p.w_row && ia < s.elems_a && ib < s.elems_b, 256);
+                            blk[c * BPU + k].add1(fa[ia], fb[ib]);
+                        }
+                }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < NB; k++) lds[lr][k][lu] = blk[k];   // (units side by side: lanes 16 or 24 bytes apart)
+    }
+}
+
+// step 2, behind a barrier: the windows of the tile; channel 0 into acc0 and channel 1 into acc1 (CH = 1: acc0 alone)
+template <typename T, int CH>
+__device__ __forceinline__ void ssim_windows(const SsimShape& s, const SsimPlane& p, const SsimTileAt& at,
+                                             const SsimBlk<T> (*lds)[4 / sizeof(T)][kSsimUnitsX], SsimLane& acc0, SsimLane& acc1) {
+    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
+    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t it = threadIdx.x + n * kSsimBlock, lu = it % kSsimUnitsX, lr = it / kSsimUnitsX, u = u0 + lu, j = j0 + lr;
+        if (lu + 1 >= (uint32_t)kSsimUnitsX || lr + 1 >= (uint32_t)kSsimRows || j + 1 >= p.bh || u * BPU + 1 >= p.bw) continue;
+#pragma unroll
+        for (uint32_t c = 0; c < (uint32_t)CH; c++) {
+            SsimBlk<T> col[BPU + 1];   // blocks (i, j) + (i, j + 1) of the unit's blocks and of the first one to the right
+#pragma unroll
+            for (uint32_t k = 0; k < BPU; k++) col[k] = lds[lr][c * BPU + k][lu] + lds[lr + 1][c * BPU + k][lu];
+            col[BPU] = lds[lr][c * BPU][lu + 1] + lds[lr + 1][c * BPU][lu + 1];   // (never written where no block is: then no window uses it)
+            SsimLane& acc = c ? acc1 : acc0;
+#pragma unroll
+            for (uint32_t k = 0; k < BPU; k++) {
+                if (u * BPU + k + 1 >= p.bw) continue;
+                const double loss = ssim_loss<T>(col[k] + col[k + 1], s.c1, s.c2);
+                acc.sum += loss; acc.mx = fmax(acc.mx, loss); acc.cnt++;
+            }
+        }
+    }
+}
+
+template <typename T, bool PLANAR>
+__global__ void __launch_bounds__(kSsimBlock) frame_ssim_kernel(const SsimArgs a) {
+    __shared__ SsimBlk<T> lds[kSsimRows][4 / sizeof(T)][kSsimUnitsX];
+    const unsigned f = blockIdx.y;
+    HF_DBG_CHECK(f < (unsigned)a.n && f < (unsigned)kMaxErrorPairs, 257);
+    const T* __restrict__ fa = static_cast<const T*>(a.a[f]);
+    const T* __restrict__ fb = static_cast<const T*>(a.b[f]);
+    const SsimShape& s = a.sh;
+    SsimLane acc[3] = {};   // Y, U, V (indexed by constants only)
+    SsimRows rows = {};
+    uint32_t t = blockIdx.x;
+    SsimTileAt at = {0, 0, 0};
+    if (t < s.tiles) { at = ssim_locate<PLANAR>(s, t); ssim_fetch<T>(fa, fb, s, s.pl[at.pl], at, rows); }
+    while (t < s.tiles) {
+        if (at.pl == 0)   ssim_sums<T, 1>(fa, fb, s, s.pl[0], at, rows, lds);
+        else if (!PLANAR) ssim_sums<T, 2>(fa, fb, s, s.pl[1], at, rows, lds);
+        else              ssim_sums<T, 1>(fa, fb, s, s.pl[at.pl], at, rows, lds);
+        __syncthreads();
+        const uint32_t tn = t + gridDim.x;
+        SsimTileAt nx = at;
+        if (tn < s.tiles) { nx = ssim_locate<PLANAR>(s, tn); ssim_fetch<T>(fa, fb, s, s.pl[nx.pl], nx, rows); }
+        if (at.pl == 0)       ssim_windows<T, 1>(s, s.pl[0], at, lds, acc[0], acc[0]);
+        else if (!PLANAR)     ssim_windows<T, 2>(s, s.pl[1], at, lds, acc[1], acc[2]);
+        else if (at.pl == 1)  ssim_windows<T, 1>(s, s.pl[1], at, lds, acc[1], acc[1]);
+        else                  ssim_windows<T, 1>(s, s.pl[2], at, lds, acc[2], acc[2]);
+        __syncthreads();   // the next tile overwrites the blocks
+        t = tn; at = nx;
+    }
+    __shared__ SsimAcc red[3][kSsimBlock / 64];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int pl = 0; pl < 3; pl++) {
+        SsimAcc p{(unsigned long long)acc[pl].sum, (unsigned long long)acc[pl].mx, acc[pl].cnt};
+        for (int o = 32; o > 0; o >>= 1) {
+            p.sum += __shfl_down(p.sum, o);
+            const unsigned long long m = __shfl_down(p.mx, o);
+            p.mx = m > p.mx ? m : p.mx;
+            p.cnt += __shfl_down(p.cnt, o);
+        }
+        if (lane == 0) red[pl][wave] = p;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned pl = threadIdx.x;
+        SsimAcc t = red[pl][0];
+        for (int w = 1; w < kSsimBlock / 64; w++) {
+            const SsimAcc& o = red[pl][w];
+            t.sum += o.sum; t.mx = o.mx > t.mx ? o.mx : t.mx; t.cnt += o.cnt;
+        }
+        FrameSsimSlot* out = a.slots + f;
+        if (t.mx) {   // (windows that are equal add nothing but their number)
+            atomicAdd(reinterpret_cast<unsigned long long*>(&out->sum_loss_q32[pl]), t.sum);
+            atomicMax(reinterpret_cast<unsigned long long*>(&out->max_loss_q32[pl]), t.mx);
+        }
+        if (t.cnt) atomicAdd(reinterpret_cast<unsigned long long*>(&out->count[pl]), (unsigned long long)t.cnt);
+    }
+}
+
 }  // namespace
 
 bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
@@ -242,6 +559,63 @@ bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool
     return true;
 }
 
+bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int n, const void* const* a,
+                       const void* const* b, FrameSsimSlot* slots, hipStream_t stream) {
+    if (n < 1 || n > kMaxErrorPairs) return false;
+    const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
+    SsimArgs k{};
+    SsimShape& s = k.sh;
+    const uint32_t hc = (uint32_t)(H / 2), wc = (uint32_t)(W / 2);
+    const uint32_t pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a, pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
+    // wide accesses: as for the error sums (the chroma bases are whole numbers of rows behind the frame's)
+    int vec_y = ((uint32_t)stride_a * bpp) % 16 == 0 && ((uint32_t)stride_b * bpp) % 16 == 0;
+    for (int i = 0; i < n; i++) {
+        k.a[i] = a[i]; k.b[i] = b[i];
+        if (!aligned16(a[i]) || !aligned16(b[i])) vec_y = 0;
+    }
+    const int vec_c = vec_y && (pitch_ca * bpp) % 16 == 0 && (pitch_cb * bpp) % 16 == 0;
+    auto plane = [&](SsimPlane& p, uint32_t w, uint32_t h, uint32_t ch, size_t base_a, size_t base_b, uint32_t pitch_a, uint32_t pitch_b, int vec) {
+        p.bw = w >> 2; p.bh = h >> 2; p.w_row = w * ch;
+        p.pitch_a = pitch_a; p.pitch_b = pitch_b; p.base_a = base_a; p.base_b = base_b; p.vec = vec;
+        const uint32_t per_tile_x = (uint32_t)(kSsimUnitsX - 1) * (EL / 4 / ch), per_tile_y = (uint32_t)(kSsimRows - 1);   // windows
+        const bool any = p.bw > 1 && p.bh > 1;
+        p.tiles_x = any ? (p.bw - 1 + per_tile_x - 1) / per_tile_x : 0;
+        p.tile_first = s.tiles;
+        s.tiles += any ? p.tiles_x * ((p.bh - 1 + per_tile_y - 1) / per_tile_y) : 0;
+    };
+    const size_t base_ca = (size_t)H * (size_t)stride_a, base_cb = (size_t)H * (size_t)stride_b;
+    plane(s.pl[0], (uint32_t)W, (uint32_t)H, 1, 0, 0, (uint32_t)stride_a, (uint32_t)stride_b, vec_y);
+    if (planar) {
+        plane(s.pl[1], wc, hc, 1, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
+        plane(s.pl[2], wc, hc, 1, base_ca + (size_t)hc * pitch_ca, base_cb + (size_t)hc * pitch_cb, pitch_ca, pitch_cb, vec_c);
+    } else {
+        plane(s.pl[1], wc, hc, 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
+    }
+    const uint32_t rows_c = planar ? 2u * hc : hc;
+    s.elems_a = base_ca + (size_t)rows_c * pitch_ca; s.elems_b = base_cb + (size_t)rows_c * pitch_cb;
+    s.c1 = c1; s.c2 = c2;
+    k.n = n;
+    k.slots = slots;
+    void (*kernel)(const SsimArgs) = hdr ? (planar ? frame_ssim_kernel<uint16_t, true> : frame_ssim_kernel<uint16_t, false>)
+                                         : (planar ? frame_ssim_kernel<uint8_t, true> : frame_ssim_kernel<uint8_t, false>);
+    // as many workgroups in the whole launch as the device holds at once (a workgroup strides over its pair's tiles: more would run in a
+    // second, mostly empty round), one at least per pair (a frame without a window: its slot stays zero)
+    static int resident[2][2];   // by kernel; asked once (the same answer from every thread)
+    int& res = resident[hdr ? 1 : 0][planar ? 1 : 0];
+    if (!res) {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSsimBlock, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) { per_cu = 2; cus = 256; }
+        res = per_cu * cus;
+    }
+    const uint32_t cap = (uint32_t)res / (uint32_t)n > 0 ? (uint32_t)res / (uint32_t)n : 1u;
+    const uint32_t want = s.tiles ? s.tiles : 1u;
+    const dim3 grid(want < cap ? want : cap, (unsigned)n);
+    if ((s.tiles + grid.x - 1) / grid.x >= kSsimMaxTilesPerWorkgroup) return false;   // (SsimLane; 2160p has 864 tiles)
+    HF_LAUNCH("frame_ssim", kernel, grid, dim3(kSsimBlock), 0, stream, k);
+    return true;
+}
+
 bool dbg_bounds_read_metrics(unsigned out[5], bool reset) {
 #ifdef HF_DEBUG_BOUNDS
     unsigned rec[5] = {0, 0, 0, 0, 0};
@@ -260,19 +634,26 @@ bool dbg_bounds_read_metrics(unsigned out[5], bool reset) {
 
 using namespace hfi;
 
+// what both enqueue calls refuse, each with nothing enqueued; n_slots: the public slot range named in the message
+static int check_pairs(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar,
+                       int first_slot, int max_slot, int n_slots) {
+    if (!a || !b) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null frame table", who);
+    if (n < 1 || n > HF_MAX_ERROR_PAIRS) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: %d pairs, one launch takes 1 .. %d", who, n, HF_MAX_ERROR_PAIRS);
+    if (first_slot < 0 || first_slot > max_slot - n) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: slots [%d, %d + %d) outside [0, %d)", who, first_slot, first_slot, n, n_slots);
+    for (int i = 0; i < n; i++)
+        if (!a[i] || !b[i]) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null frame in pair %d", who, i);
+    if (stride_a < c->g.W || stride_b < c->g.W) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: strides %d / %d below the frame width %d", who, stride_a, stride_b, c->g.W);
+    if (planar && ((stride_a | stride_b) & 1)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: planar frames need even strides (%d / %d)", who, stride_a, stride_b);
+    return HF_OK;
+}
+
 // slots [first, first + n) zeroed, then pair i compared into slot first + i -- behind everything the context has enqueued: warps on a
 // second stream (HF_FLAG_DUAL_STREAM) are waited for like hf_download_frame_device does, a batch member issues on the batch's stream.
 // max_slot: HF_ERROR_SLOTS for the public range, one more for hf_frame_error's own slot.
 static int enqueue_errors(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar,
                           int first_slot, int max_slot) {
     HF_CHECK_CTX(c);
-    if (!a || !b) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null frame table", who);
-    if (n < 1 || n > HF_MAX_ERROR_PAIRS) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: %d pairs, one launch takes 1 .. %d", who, n, HF_MAX_ERROR_PAIRS);
-    if (first_slot < 0 || first_slot > max_slot - n) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: slots [%d, %d + %d) outside [0, %d)", who, first_slot, first_slot, n, HF_ERROR_SLOTS);
-    for (int i = 0; i < n; i++)
-        if (!a[i] || !b[i]) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null frame in pair %d", who, i);
-    if (stride_a < c->g.W || stride_b < c->g.W) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: strides %d / %d below the frame width %d", who, stride_a, stride_b, c->g.W);
-    if (planar && ((stride_a | stride_b) & 1)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: planar frames need even strides (%d / %d)", who, stride_a, stride_b);
+    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, HF_ERROR_SLOTS)) return rc;
     if (int rc = set_device(c)) return rc;
     if (!c->error_slots) HF_HIP(c, alloc_device(c->error_slots, (size_t)(HF_ERROR_SLOTS + 1) * sizeof(hf::FrameErrorSlot)));
     if (int rc = leave_warp_stream(c)) return rc;
@@ -295,6 +676,39 @@ static int read_errors(hf_ctx* c, int first_slot, int n, int max_slot, struct hf
     return sync_ctx(c);
 }
 
+// The windowed SSIM of the same pairs into slots of its own: ordered, refused and read like the error sums.  peak 0: the format's own.
+static int enqueue_ssim(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar, int peak,
+                        int first_slot, int max_slot) {
+    HF_CHECK_CTX(c);
+    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, HF_SSIM_SLOTS)) return rc;
+    const int top = c->g.hdr ? 65535 : 255;
+    if (peak < 0 || peak > top) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: peak %d outside 1 .. %d (0: the format's own)", who, peak, top);
+    const long long pk = peak ? peak : !c->g.hdr ? 255 : planar ? 1023 : 65535;
+    const long long c1 = (64 * pk * pk + 5000) / 10000, c2 = (9 * 64 * 63 * pk * pk + 5000) / 10000;
+    if (int rc = set_device(c)) return rc;
+    const bool fresh = !c->ssim_slots;
+    if (fresh) HF_HIP(c, alloc_device(c->ssim_slots, (size_t)(HF_SSIM_SLOTS + 1) * sizeof(hf::FrameSsimSlot)));
+    if (int rc = leave_warp_stream(c)) return rc;
+    if (fresh) HF_HIP(c, hipMemsetAsync(c->ssim_slots.get(), 0, (size_t)(HF_SSIM_SLOTS + 1) * sizeof(hf::FrameSsimSlot), c->stream));   // a slot never used reads as zeros
+    hf::FrameSsimSlot* slots = c->ssim_slots.get() + first_slot;
+    HF_HIP(c, hipMemsetAsync(slots, 0, (size_t)n * sizeof(hf::FrameSsimSlot), c->stream));
+    if (!hf::launch_frame_ssim(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, n, a, b, slots, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
+    HF_HIP(c, hipGetLastError());
+    return HF_OK;
+}
+
+static int read_ssim(hf_ctx* c, int first_slot, int n, int max_slot, struct hf_frame_ssim* out) {
+    HF_CHECK_CTX(c);
+    if (!out || n < 1 || first_slot < 0 || first_slot > max_slot - n)
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_ssim_read: slots [%d, %d + %d) outside [0, %d), or null", first_slot, first_slot, n, HF_SSIM_SLOTS);
+    if (!c->ssim_slots) return fail(c, HF_ERR_STATE, "hf_frame_ssim_read: nothing was enqueued");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    HF_HIP(c, hipMemcpyAsync(out, c->ssim_slots.get() + first_slot, (size_t)n * sizeof(struct hf_frame_ssim), hipMemcpyDeviceToHost, c->stream));
+    return sync_ctx(c);
+}
+
 extern "C" {
 
 int hf_frame_error_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
@@ -309,6 +723,20 @@ int hf_frame_error(hf_ctx* c, const void* device_a, const void* device_b, int st
     if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_error: null result");
     if (int rc = enqueue_errors(c, "hf_frame_error", 1, &device_a, &device_b, stride_a, stride_b, planar, HF_ERROR_SLOTS, HF_ERROR_SLOTS + 1)) return rc;
     return read_errors(c, HF_ERROR_SLOTS, 1, HF_ERROR_SLOTS + 1, out);
+}
+
+int hf_frame_ssim_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
+                          int peak, int first_slot) {
+    return enqueue_ssim(c, "hf_frame_ssim_enqueue", n, device_a, device_b, stride_a, stride_b, planar, peak, first_slot, HF_SSIM_SLOTS);
+}
+
+int hf_frame_ssim_read(hf_ctx* c, int first_slot, int n, struct hf_frame_ssim* out) { return read_ssim(c, first_slot, n, HF_SSIM_SLOTS, out); }
+
+int hf_frame_ssim(hf_ctx* c, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar, int peak, struct hf_frame_ssim* out) {
+    HF_CHECK_CTX(c);
+    if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_ssim: null result");
+    if (int rc = enqueue_ssim(c, "hf_frame_ssim", 1, &device_a, &device_b, stride_a, stride_b, planar, peak, HF_SSIM_SLOTS, HF_SSIM_SLOTS + 1)) return rc;
+    return read_ssim(c, HF_SSIM_SLOTS, 1, HF_SSIM_SLOTS + 1, out);
 }
 
 }  // extern "C"

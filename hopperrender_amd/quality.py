@@ -1,6 +1,6 @@
 """Leave-one-out interpolation quality of a clip, measured on the device.
 
-    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--report out.json]
+    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--report out.json]
     python -m hopperrender_amd.quality clip.nv12 --width 1920 --height 1080 [--hdr | --pix-fmt yuv420p10le] ...
 
 Every second frame of the clip is withheld: the sources S_j = frames[2 j] go through one asynchronous context exactly as a filter would
@@ -22,6 +22,15 @@ each period with no host sync and read once per chunk of 128 pairs -- once at th
 The report is a plain dict (json.dump-able): per evaluated pair and plane the integer sums and psnr = 10 log10(peak^2 count / sse)
 (peak 255 or 65535; None where sse == 0) for the interpolation and for the repeat baseline, clip aggregates (PSNR of the summed sse, the
 worst pair), the settings, and -- on request -- what the filter's scene-change detection would have made of each period.
+
+--ssim / evaluate(ssim=True) adds the windowed SSIM (hf_frame_ssim_enqueue: 8 x 8 windows at stride 4, the block form of x264 and of FFmpeg's
+ssim filter, in integers) beside every error sum, on the same pairs and slot numbers, read once per chunk like them.  PSNR alone rewards
+smoothing -- a larger blur radius, or a blend that averages two frames, trades a sharp and slightly misplaced edge for a ghost and the
+squared error falls -- and cannot tell a frame a little wrong everywhere from one torn in a single place; SSIM is the second judge for
+exactly the knobs a sweep turns.  Per plane the report gains sum_loss_q32, max_loss_q32, count (loss = 2^32 - round(ssim 2^32) per window)
+and the floats ssim = 1 - sum / 2^32 / count (the mean) and min_ssim = 1 - max / 2^32 (the worst window), None where there is no window;
+the clip aggregates are summed loss over summed count and the largest loss; gain_ssim_y per pair and for the clip is interpolation
+minus repeat, and clip["worst_pair_ssim"] names the pair with the lowest mean Y.  Without it the report is what it was.
 """
 import argparse
 import itertools
@@ -31,6 +40,7 @@ import sys
 
 PLANES = ("Y", "U", "V")
 SUMS = ("sse", "sad", "max_abs", "n_differ", "count")
+SSIM_SUMS = ("sum_loss_q32", "max_loss_q32", "count")
 SETTINGS = {"search_radius": 16, "delta_scalar": 8, "neighbor_scalar": 6, "blur_radius": 0, "iterations": 0, "max_calc_res": 270}
 PAIRS_PER_READ = 128   # two result slots per pair (interpolation, repeat) out of HF_ERROR_SLOTS
 
@@ -97,12 +107,35 @@ def _aggregate(rows, key, peak):
     return out
 
 
+def _ssim_floats(total, worst, count):
+    return {"ssim": 1.0 - total / 4294967296.0 / count if count else None, "min_ssim": 1.0 - worst / 4294967296.0 if count else None}
+
+
+def _add_ssim(planes, got):
+    """the SSIM integers of one slot and the floats derived from them, into a pair's plane dicts (their "count" stays the elements compared)"""
+    for p in PLANES:
+        total, worst, count = (int(got[p][k]) for k in SSIM_SUMS)
+        planes[p].update({"sum_loss_q32": total, "max_loss_q32": worst, "ssim_count": count}, **_ssim_floats(total, worst, count))
+
+
+def _add_ssim_aggregate(agg, rows, key):
+    for p in PLANES:
+        total, count = sum(r[key][p]["sum_loss_q32"] for r in rows), sum(r[key][p]["ssim_count"] for r in rows)
+        worst = max(r[key][p]["max_loss_q32"] for r in rows)
+        agg[p].update({"sum_loss_q32": total, "max_loss_q32": worst, "ssim_count": count}, **_ssim_floats(total, worst, count))
+
+
+def _minus(a, b):
+    return None if a is None or b is None else a - b
+
+
 def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
-             device_index=0, device=None, **settings):
+             device_index=0, device=None, ssim=False, **settings):
     """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
     settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
     library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
-    scene-change detection would have taken per period (costs one wait per period; the outputs evaluated are always the warps)."""
+    scene-change detection would have taken per period (costs one wait per period; the outputs evaluated are always the warps).
+    ssim: also score every comparison with the device's windowed SSIM (module docstring); off, nothing of it is called or reported."""
     unknown = set(settings) - set(SETTINGS)
     if unknown:
         raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
@@ -159,6 +192,8 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                 main.interpolatePeriod(b.ptr, [0.5], [out.ptr], 2)
                 if s["evaluated"]:
                     main.frameErrorEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
+                    if ssim:
+                        main.frameSsimEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
                     slot += 2
                 if filt is not None:
                     main.waitFlow()
@@ -167,11 +202,16 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     cuts.append({"period": s["period"], "pair": s["pair"], "total_frame_delta": delta,
                                  "kind": "copy" if filt.detect(fc) else "warp"})
             got = main.frameErrorRead(0, slot) if slot else []
+            got_ssim = main.frameSsimRead(0, slot) if ssim and slot else []
             for i, s in enumerate(s for s in chunk if s["evaluated"]):
                 row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
                        "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
                 a, r = row["interpolated"]["Y"]["psnr"], row["repeat"]["Y"]["psnr"]
                 row["gain_db_y"] = None if a is None or r is None else a - r
+                if ssim:
+                    _add_ssim(row["interpolated"], got_ssim[2 * i])
+                    _add_ssim(row["repeat"], got_ssim[2 * i + 1])
+                    row["gain_ssim_y"] = _minus(row["interpolated"]["Y"]["ssim"], row["repeat"]["Y"]["ssim"])
                 rows.append(row)
             # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
             last = chunk[-1]["period"]
@@ -189,6 +229,12 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
             "worst_pair": {"pair": worst["pair"], "psnr_y": worst["interpolated"]["Y"]["psnr"]}}
     a, r = clip["interpolated"]["Y"]["psnr"], clip["repeat"]["Y"]["psnr"]
     clip["gain_db_y"] = None if a is None or r is None else a - r
+    if ssim:
+        _add_ssim_aggregate(clip["interpolated"], rows, "interpolated")
+        _add_ssim_aggregate(clip["repeat"], rows, "repeat")
+        clip["gain_ssim_y"] = _minus(clip["interpolated"]["Y"]["ssim"], clip["repeat"]["Y"]["ssim"])
+        low = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["ssim"] is None else r["interpolated"]["Y"]["ssim"])
+        clip["worst_pair_ssim"] = {"pair": low["pair"], "ssim_y": low["interpolated"]["Y"]["ssim"]}
     return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
             "settings": dict(st, black_level=float(black), white_level=float(white)),
             "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
@@ -257,6 +303,8 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--sweep", action="append", metavar="KEY=v1,v2,...",
                     help="evaluate every value of a knob (radius, delta, neighbor, blur, iterations, max-calc-res); repeatable: the cartesian product")
+    ap.add_argument("--ssim", action="store_true",
+                    help="also score every comparison with the windowed SSIM (8 x 8 windows at stride 4): mean and worst window per plane")
     ap.add_argument("--report", default=None, help="write the reports as JSON")
     a = ap.parse_args(argv)
     if a.pix_fmt is None:
@@ -276,6 +324,10 @@ def _db(x):
     return "  equal" if x is None else f"{x:7.3f}"
 
 
+def _ss(x):
+    return "  none" if x is None else f"{x:6.4f}"
+
+
 def main(argv=None, device=None):
     """Evaluates the clip once per setting of the sweep (once without --sweep), prints one line per setting; returns the reports."""
     from .cli import PIX_FMTS, _Clip
@@ -289,13 +341,16 @@ def main(argv=None, device=None):
         st = dict(base, **sweep)
         rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
                        scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
-                       device=device, **st)
+                       device=device, ssim=a.ssim, **st)
         reports.append(rep)
         c = rep["clip"]
         knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
         print(f"{knobs}  pairs {len(rep['pairs'])}  PSNR Y/U/V {_db(c['interpolated']['Y']['psnr'])} {_db(c['interpolated']['U']['psnr'])} "
               f"{_db(c['interpolated']['V']['psnr'])} dB  repeat Y {_db(c['repeat']['Y']['psnr'])} dB  gain {_db(c['gain_db_y'])} dB  "
-              f"worst pair {c['worst_pair']['pair']} ({_db(c['worst_pair']['psnr_y'])} dB)")
+              f"worst pair {c['worst_pair']['pair']} ({_db(c['worst_pair']['psnr_y'])} dB)" + (
+                  f"  SSIM Y/U/V {_ss(c['interpolated']['Y']['ssim'])} {_ss(c['interpolated']['U']['ssim'])} {_ss(c['interpolated']['V']['ssim'])}  "
+                  f"repeat Y {_ss(c['repeat']['Y']['ssim'])}  worst window {_ss(c['interpolated']['Y']['min_ssim'])}  "
+                  f"worst pair {c['worst_pair_ssim']['pair']} ({_ss(c['worst_pair_ssim']['ssim_y'])})" if a.ssim else ""))
     if a.report:
         with open(a.report, "w") as f:
             json.dump({"input": a.input, "reports": reports}, f, indent=1)

@@ -393,6 +393,47 @@ int hf_frame_error_read(hf_ctx* ctx, int first_slot, int n, struct hf_frame_erro
 int hf_frame_error(hf_ctx* ctx, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar,
                    struct hf_frame_error* out);
 
+/* ---- Windowed SSIM on the device, beside the frame error sums ----
+ * PSNR rewards smoothing (a ghost of two averaged frames scores above a sharp, slightly misplaced edge) and cannot tell a frame that is
+ * a little wrong everywhere from one torn in a single place; structural similarity over small windows is the usual second judge, as a
+ * mean and as a worst window.  This is the block form of x264 and of FFmpeg's `ssim` filter, with every step pinned so that the result
+ * is a set of integers anyone can reproduce.  The pairs, strides, layouts and planes are those of hf_frame_error_enqueue; per plane of
+ * w x h compared elements (padding columns are never read):
+ *   1. Blocks.  bw = w >> 2, bh = h >> 2; block (i, j) covers rows 4 j .. 4 j + 3 and columns 4 i .. 4 i + 3 (the trailing w & 3 columns
+ *      and h & 3 rows are not used).  Per block, in integers:  s1 = sum a,  s2 = sum b,  ss = sum (a^2 + b^2),  s12 = sum a b.
+ *   2. Windows.  Window (i, j), 0 <= i < bw - 1, 0 <= j < bh - 1, is the 2 x 2 blocks (i, j) .. (i + 1, j + 1) -- 8 x 8 elements at
+ *      stride 4; S1, S2, SS, S12 are the sums over its four blocks.  count = (bw - 1) (bh - 1), or 0 if bw < 2 or bh < 2.
+ *   3. Constants, integers, with integer division:  c1 = (64 peak^2 + 5000) / 10000,  c2 = (9 * 64 * 63 peak^2 + 5000) / 10000
+ *      (peak 255: 416 and 235963, FFmpeg's 8-bit constants; 65535: 27486952 and 15585101693; 1023: 6698 and 3797644).
+ *   4. Window terms, in 64-bit integers (each stays below 2^53 in magnitude, so its conversion to double is exact):
+ *          vars = 64 SS - S1^2 - S2^2      covar = 64 S12 - S1 S2
+ *          A = 2 S1 S2 + c1      B = 2 covar + c2      C = S1^2 + S2^2 + c1      D = vars + c2
+ *   5. Window score:  ssim = (double(A) * double(B)) / (double(C) * double(D)) -- two IEEE multiplications and one IEEE division, no
+ *      contraction;  q = llrint(ssim * 2^32), round to nearest even (the multiplication is exact);  loss = 2^32 - q, an unsigned integer
+ *      in [0, 2^33], 0 where the two windows are equal (then A == C and B == D).
+ *   6. Per plane:  sum_loss_q32 = sum of loss,  max_loss_q32 = largest loss,  count.  Mean SSIM = 1 - sum_loss_q32 / 2^32 / count, worst
+ *      window = 1 - max_loss_q32 / 2^32.  Integer sums: exact, independent of the order of addition; equal frames give zero losses.
+ * peak: 0 selects 255 on an 8-bit context, 65535 on a 16-bit one with planar = 0 and 1023 with planar = 1 (LSB-aligned yuv420p10le);
+ * otherwise 1 .. 255 on 8 bit and 1 .. 65535 on 16 bit.  (A peak below 9 makes c1 zero: a window that is zero on both sides then has
+ * no score, 0 / 0, and what it adds is unspecified.)
+ *   hf_frame_ssim_enqueue  only enqueues, ordered exactly like hf_frame_error_enqueue (behind every warp, copy and update of ctx, the
+ *                          warp stream of an HF_FLAG_DUAL_STREAM context included; a batch member on its batch's stream): zeroes SSIM
+ *                          slots [first_slot, first_slot + n) and scores pair i into slot first_slot + i.  The SSIM slots are their own:
+ *                          the error slots of the same numbers are untouched.
+ *   hf_frame_ssim_read     waits for ctx's work and copies n slots out; HF_ERR_STATE before any enqueue.
+ *   hf_frame_ssim          one pair, blocking; uses a slot of its own outside [0, HF_SSIM_SLOTS).
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued: everything hf_frame_error_enqueue refuses (with HF_SSIM_SLOTS as the slot bound), and
+ * a peak outside its range.  The slots (18 KB) are allocated on first use and freed with the context.  Additive to ABI version 6. */
+#define HF_SSIM_SLOTS 256
+struct hf_frame_ssim {   /* index 0 Y, 1 U, 2 V; a struct tag only, like hf_frame_error */
+    uint64_t sum_loss_q32[3], max_loss_q32[3], count[3];
+};
+int hf_frame_ssim_enqueue(hf_ctx* ctx, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b,
+                          int planar, int peak, int first_slot);
+int hf_frame_ssim_read(hf_ctx* ctx, int first_slot, int n, struct hf_frame_ssim* out);
+int hf_frame_ssim(hf_ctx* ctx, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar, int peak,
+                  struct hf_frame_ssim* out);
+
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
 /* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
