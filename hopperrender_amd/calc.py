@@ -197,6 +197,25 @@ class OpticalFlowCalc:
                                             int(stride_b) or self.m_frameWidth, 1 if planar else 0, C.byref(e)), self._ctx)
         return self._frame_error_dict(e)
 
+    # ---- per-tile error maps on the device (hf_frame_error_map*) ----
+    def frameErrorMapShape(self, tile):
+        """hf_frame_error_map_shape: (tiles_x, tiles_y, bytes of one map) of this context's geometry for tiles of `tile` luma pixels."""
+        tw, th, nbytes = C.c_int(), C.c_int(), C.c_size_t()
+        capi.check(self._lib.hf_frame_error_map_shape(self._ctx, int(tile), C.byref(tw), C.byref(th), C.byref(nbytes)), self._ctx)
+        return tw.value, th.value, nbytes.value
+
+    def frameErrorMapEnqueue(self, a_ptrs, b_ptrs, tile, maps_ptr, stride_a=0, stride_b=0, planar=False):
+        """hf_frame_error_map_enqueue: the per-tile error sums of device frames a_ptrs[i] against b_ptrs[i] into map i of the device buffer
+        at maps_ptr (len(a_ptrs) maps of frameErrorMapShape(tile)[2] bytes, 16-byte aligned), behind everything this context has
+        enqueued; only enqueues.  Download the buffer after sync() and view it with frame_error_maps()."""
+        n = len(a_ptrs)
+        if len(b_ptrs) != n:
+            raise ValueError("frameErrorMapEnqueue: as many b frames as a frames")
+        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
+        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
+        capi.check(self._lib.hf_frame_error_map_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
+                                                        1 if planar else 0, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
+
     # ---- windowed SSIM on the device (hf_frame_ssim*) ----
     @staticmethod
     def _frame_ssim_dict(e):
@@ -329,6 +348,19 @@ class OpticalFlowCalcSDR(OpticalFlowCalc):
 class OpticalFlowCalcHDR(OpticalFlowCalc):
     """P010, 16-bit (opticalFlowCalcHDR.h:10-56)."""
     is_hdr = True
+
+
+ERROR_TILE_DTYPE = np.dtype([("sse", "<u8"), ("sad", "<u4"), ("max_abs", "<u4")])   # struct hf_error_tile
+
+
+def frame_error_maps(raw, n, tiles_x, tiles_y):
+    """A downloaded map buffer of hf_frame_error_map_enqueue (bytes, or any array of n * 48 * tiles_y * tiles_x bytes) as a structured
+    array [n][3][tiles_y][tiles_x] with fields sse, sad, max_abs; plane 0 Y, 1 U, 2 V.  A view, no copy."""
+    a = np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw).reshape(-1).view(np.uint8)
+    need = n * 3 * tiles_y * tiles_x * ERROR_TILE_DTYPE.itemsize
+    if a.size < need:
+        raise ValueError(f"frame_error_maps: {a.size} bytes, {n} maps of 3 x {tiles_y} x {tiles_x} tiles need {need}")
+    return a[:need].view(ERROR_TILE_DTYPE).reshape(n, 3, tiles_y, tiles_x)
 
 
 class DeviceBuffer:

@@ -29,6 +29,7 @@ HF_MAX_PERIOD_OUTPUTS_WIDE = 24   # the *_wide period calls: 23.976 fps -> 480 H
 HF_MAX_ERROR_PAIRS = 192          # frame pairs of one hf_frame_error_enqueue launch
 HF_ERROR_SLOTS = 256              # result slots of a context
 HF_SSIM_SLOTS = 256               # result slots of hf_frame_ssim_enqueue, a range of their own
+HF_ERROR_MAP_TILES = (16, 32, 64)  # tile edges of hf_frame_error_map_enqueue, luma pixels
 
 (HF_OK, HF_ERR_INVALID_ARGUMENT, HF_ERR_NO_DEVICE, HF_ERR_OUT_OF_MEMORY, HF_ERR_HIP, HF_ERR_STATE) = (0, -1, -2, -3, -4, -5)
 
@@ -96,6 +97,11 @@ class HfFrameError(C.Structure):
 class HfFrameSsim(C.Structure):
     """struct hf_frame_ssim: summed and largest window loss (2^32 - round(ssim 2^32)) and window count of one frame pair, index 0 Y, 1 U, 2 V"""
     _fields_ = [("sum_loss_q32", C.c_uint64 * 3), ("max_loss_q32", C.c_uint64 * 3), ("count", C.c_uint64 * 3)]
+
+
+class HfErrorTile(C.Structure):
+    """struct hf_error_tile: the integer error sums of one tile of one plane (hf_frame_error_map_enqueue), 16 bytes"""
+    _fields_ = [("sse", C.c_uint64), ("sad", C.c_uint32), ("max_abs", C.c_uint32)]
 
 
 class HfDebugCounters(C.Structure):
@@ -180,6 +186,8 @@ SIGNATURES = {
     "hf_frame_error_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i]),
     "hf_frame_error_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameError)]),
     "hf_frame_error": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(HfFrameError)]),
+    "hf_frame_error_map_shape": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)]),
+    "hf_frame_error_map_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "hf_frame_ssim_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "hf_frame_ssim_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameSsim)]),
     "hf_frame_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(HfFrameSsim)]),

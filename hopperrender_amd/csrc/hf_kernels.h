@@ -200,6 +200,11 @@ struct FrameErrorSlot {
 constexpr int kMaxErrorPairs = 192;
 bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
                          FrameErrorSlot* slots, hipStream_t stream);
+// Per-tile error maps (hf_metrics.hip; hf_frame_error_map*): the same pairs, strides and layouts; maps = n maps of hf_error_tile
+// [3][th][tw] (include/hopperflow.h), 16-byte aligned, every entry of which the launch stores -- nothing to zero.  false: nothing launched
+// (tile not 16, 32 or 64, n out of range, a frame beyond 2^32 work items).
+bool launch_frame_error_map(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int tile, int n, const void* const* a,
+                            const void* const* b, void* maps, hipStream_t stream);
 // Windowed SSIM (hf_metrics.hip; hf_frame_ssim*): the same pairs, strides and layouts as launch_frame_errors; per plane the summed and the
 // largest loss 2^32 - round(ssim 2^32) over the 8 x 8 windows at stride 4 and their number, with the integer constants c1, c2 of the peak
 // (include/hopperflow.h has the definition).  The layout of hf_frame_ssim; slots zeroed by the caller on the same stream.

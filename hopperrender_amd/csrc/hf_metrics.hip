@@ -18,7 +18,10 @@
 // workgroup's waves (LDS), and ONE atomicAdd / atomicMax per quantity, plane and workgroup into the pair's slot, which a hipMemsetAsync
 // ahead of the launch zeroed.  Grid-stride over at most ~2048 workgroups per launch, one at least per pair.
 //
-// Further down: the windowed SSIM of the same pairs (hf_frame_ssim*), with its own kernel, launcher and slots.
+// Further down: the windowed SSIM of the same pairs (hf_frame_ssim*), with its own kernel, launcher and slots; and the per-tile error
+// maps (hf_frame_error_map*): the same sums per tile of 16, 32 or 64 luma pixels; a workgroup reads a band of tile rows in memory
+// order, a tile's lanes are reduced by shuffles (and waves that shared its rows through LDS), every entry is stored once -- no atomics,
+// no memset.  The lane mapping is described there.
 #include <type_traits>
 
 #include "hf_ctx.h"
@@ -512,13 +515,199 @@ __global__ void __launch_bounds__(kSsimBlock) frame_ssim_kernel(const SsimArgs a
     }
 }
 
-}  // namespace
+// ---- Per-tile error maps (hf_frame_error_map*; the definition is in include/hopperflow.h) ----
+// The error sums above per tile of `tile` x `tile` luma pixels (16, 32 or 64) and plane: one hf_error_tile {sse, sad, max_abs} each, in
+// one caller-owned buffer for all pairs of the launch.  Same pointer table, layouts, pitches and work item (16 bytes of a row on each
+// side, wide where every frame of the launch is aligned, element by element otherwise) as the error kernel, whose ErrorShape, Part,
+// add_word and row_item it uses as they are.
+//
+// The mapping.  A BAND is the `tile` luma rows of one tile row and the tile / 2 chroma rows under them.  A workgroup (4 waves) owns a
+// band of its pair -- blockIdx.x is the band, so workgroups start in the order of the bands in memory -- and reads it the way it lies
+// there: a plane's rows one after the other, each row by neighbouring lanes, 16 bytes a lane.  Rows of more than 128 items (2 KB) are
+// SWEPT 256 items at a time by the four waves side by side, every wave walking all rows of its 64 items; rows of 65 .. 128 items take two
+// waves side by side and the other two the odd rows; shorter rows one wave, and each wave every fourth row.  A lane keeps ONE Part
+// over all its rows (at most 64: 64 x 8 squares of 8-bit differences stay far below 2^32).  A tile is 2^lg = tile bytes-per-element /
+// 16 items across (1 .. 8), a power of two that divides 64: the lanes of a tile are neighbours inside one wave, and an item never
+// straddles two tiles -- but for the two cases below.  So a tile's lanes are reduced by lg xor-shuffle steps; where the rows were dealt
+// to several waves, those add up through LDS (one 16-byte entry per wave and tile, two buffers in turn so that one barrier per sweep
+// is enough: the waves of the first rows read buffer k & 1 while the next sweep fills the other); and the tile's first lane writes the
+// entry as one 16-byte store (neighbouring tiles: neighbouring stores).  Every tile of every plane belongs to exactly one workgroup,
+// nothing is added in device memory -- no atomics, no memset -- and every entry is stored exactly once, zeros included.
+//   interleaved UV   an item holds U (even columns) and V (odd columns) of ONE tile: Part keeps the parities apart already, each
+//                    goes to its own plane's entry (MODE 1: two values per lane)
+//   planar, 8 bit, tile 16   a chroma tile row is 8 bytes, an item holds TWO tiles: its halves are summed apart (row_item_halves) and
+//                    nothing is shuffled (MODE 2: two values per lane, tiles 2 seg and 2 seg + 1)
+// What was measured on the way is in DESIGN.md ("Per-tile error maps"): two mappings that cut a band into strips of 64 items (1 KB of
+// a row) -- the rows of a strip dealt to the four waves and combined through LDS, or a strip per wave with neither LDS nor barrier --
+// both ran at 1.3 x the error launch at tile 16: not the barrier but the strips were the cost, 1 KB read from every row, where the
+// error kernel's workgroups read 4 KB runs in memory order.  Hence whole rows.
+// Why not a tile per wave: at tile 16 of 8-bit elements a tile row is ONE item, 16 lanes of a wave would have work and each would read
+// 16 bytes of a line of 128.
+// LDS: 2 x 4 x 2 x 64 entries = 16 KB a workgroup, no limit below the 8 workgroups a CU holds by waves.
+constexpr int kMapBlock = 256, kMapWaves = kMapBlock / 64;
+constexpr int kMapMaxBlocks = 1 << 16;   // (341 bands a pair at kMaxErrorPairs: 5456 rows at tile 16)
 
-bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
-                         FrameErrorSlot* slots, hipStream_t stream) {
+struct alignas(16) TileSum {   // the layout of hf_error_tile
+    unsigned long long sse;
+    uint32_t sad, mx;
+};
+static_assert(sizeof(TileSum) == sizeof(struct hf_error_tile) && offsetof(TileSum, sad) == offsetof(struct hf_error_tile, sad) &&
+              offsetof(TileSum, mx) == offsetof(struct hf_error_tile, max_abs), "TileSum is hf_error_tile");
+
+struct MapArgs {
+    ErrorShape sh;
+    int n;
+    uint32_t rows_y;                 // H
+    uint32_t tile, lg;               // tile edge in luma pixels; a luma tile is 2^lg work items across
+    uint32_t tw, th;
+    size_t entries;                  // n 3 th tw (debug-bounds)
+    TileSum* maps;                   // [n][3][th][tw]
+    const void* a[kMaxErrorPairs];
+    const void* b[kMaxErrorPairs];
+};
+static_assert(sizeof(MapArgs) <= 4096, "kernel arguments: 4 KB");
+
+struct MapPass {         // the rows of one band in one plane (interleaved UV: in both)
+    size_t base_a, base_b;           // the plane's first row, elements
+    uint32_t pitch_a, pitch_b, w, segs;
+    uint32_t r0, r1;                 // the band's rows of the plane
+    int vec;
+    uint32_t lg;                     // a tile of the plane is 2^lg items across (MODE 2: unused, a tile is half an item)
+    uint32_t pl;                     // plane of a lane's first value
+};
+
+template <typename P>
+__device__ __forceinline__ TileSum tile_sum(const P& p, int par) { return TileSum{p.sse[par], p.sad[par], p.max_abs(par)}; }
+__device__ __forceinline__ void merge(TileSum& t, const TileSum& o) { t.sse += o.sse; t.sad += o.sad; t.mx = o.mx > t.mx ? o.mx : t.mx; }
+
+// row_item for 8-bit rows whose tiles are 8 elements across: bytes 0 .. 7 of the item into lo, 8 .. 15 into hi
+template <int SITE>
+__device__ __forceinline__ void row_item_halves(const uint8_t* __restrict__ ra, const uint8_t* __restrict__ rb, size_t oa, size_t ob, const ErrorShape& s,
+                                                uint32_t seg, uint32_t w, int vec, Part<uint8_t>& lo, Part<uint8_t>& hi) {
+    const uint32_t x0 = seg * 16u;
+    if (vec && x0 + 16u <= w) {
+        HF_DBG_CHECK(oa + x0 + 16u <= s.elems_a && ob + x0 + 16u <= s.elems_b, SITE + 0);
+        const uint4 va = *reinterpret_cast<const uint4*>(ra + x0), vb = *reinterpret_cast<const uint4*>(rb + x0);
+        add_word<uint8_t>(lo, va.x, vb.x); add_word<uint8_t>(lo, va.y, vb.y); add_word<uint8_t>(hi, va.z, vb.z); add_word<uint8_t>(hi, va.w, vb.w);
+        return;
+    }
+    const uint32_t x1 = x0 + 16u < w ? x0 + 16u : w, xm = x0 + 8u < x1 ? x0 + 8u : x1;
+    for (uint32_t x = x0; x < x1; x++) {
+        HF_DBG_CHECK(oa + x < s.elems_a && ob + x < s.elems_b, SITE + 1);
+        const uint32_t a = ra[x], b = rb[x], d = a > b ? a - b : b - a;
+        if (x < xm) lo.template add<0>(d); else hi.template add<0>(d);
+    }
+}
+
+// the finished values of a lane: the entries of its tile(s), where the frame has such a tile
+template <int MODE, int NV>
+__device__ __forceinline__ void store_tiles(const MapArgs& a, const MapPass& ps, unsigned f, uint32_t j, uint32_t seg, const TileSum (&v)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        const uint32_t tx = MODE == 2 ? 2u * seg + (uint32_t)k : seg >> ps.lg;
+        const uint32_t pl = MODE == 1 ? ps.pl + (uint32_t)k : ps.pl;
+        if (tx < a.tw) {
+            const size_t at = (((size_t)f * 3u + pl) * a.th + j) * a.tw + tx;
+            HF_DBG_CHECK(at < a.entries && pl < 3u && j < a.th, 267);
+            *reinterpret_cast<uint4*>(a.maps + at) = uint4{(uint32_t)v[k].sse, (uint32_t)(v[k].sse >> 32), v[k].sad, v[k].mx};
+        }
+    }
+}
+
+// One plane's rows of band j, by the whole workgroup.  MODE 0: a lane's item lies in one tile of plane ps.pl; 1: interleaved UV, the
+// even columns in plane ps.pl and the odd ones in the next; 2: the two halves of the item in two tiles of plane ps.pl.
+// step counts the workgroup's trips through LDS (which buffer); every branch around a barrier or a shuffle is uniform.
+template <typename T, int MODE, int SITE>
+__device__ __forceinline__ void map_pass(const T* __restrict__ fa, const T* __restrict__ fb, const MapArgs& a, const MapPass& ps, unsigned f, uint32_t j,
+                                         TileSum (*red)[kMapWaves][2][64], uint32_t& step) {
+    constexpr int NV = MODE == 0 ? 1 : 2;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lg_wa = ps.segs > 128u ? 2u : ps.segs > 64u ? 1u : 0u;            // 4, 2 or 1 waves side by side ...
+    const uint32_t wa = 1u << lg_wa, phases = (uint32_t)kMapWaves >> lg_wa;          // ... and the rows dealt to 1, 2 or 4 of them
+    const uint32_t wc = wave & (wa - 1u), ph = wave >> lg_wa;
+    const uint32_t across = 1u << ps.lg;                                             // lanes of a tile (MODE 2: unused)
+    const uint32_t slots = MODE == 2 ? 64u : 64u >> ps.lg;                           // lanes of a wave that hold finished values
+    const uint32_t sweeps = (ps.segs + 64u * wa - 1u) / (64u * wa);
+    for (uint32_t c = 0; c < sweeps; c++) {
+        const uint32_t seg0 = (c * wa + wc) * 64u, seg = seg0 + lane;
+        Part<T> p, q;
+        if (seg < ps.segs) {
+            for (uint32_t r = ps.r0 + ph; r < ps.r1; r += phases) {
+                const size_t oa = ps.base_a + (size_t)r * ps.pitch_a, ob = ps.base_b + (size_t)r * ps.pitch_b;
+                if constexpr (MODE == 2) row_item_halves<SITE>(fa + oa, fb + ob, oa, ob, a.sh, seg, ps.w, ps.vec, p, q);
+                else (void)row_item<T, SITE>(fa + oa, fb + ob, oa, ob, a.sh, seg, ps.w, ps.vec, p);
+            }
+        }
+        TileSum v[NV];
+        if constexpr (MODE == 0) { v[0] = tile_sum(p, 0); merge(v[0], tile_sum(p, 1)); }
+        if constexpr (MODE == 1) { v[0] = tile_sum(p, 0); v[1] = tile_sum(p, 1); }
+        if constexpr (MODE == 2) { v[0] = tile_sum(p, 0); merge(v[0], tile_sum(p, 1)); v[1] = tile_sum(q, 0); merge(v[1], tile_sum(q, 1)); }
+        if constexpr (MODE != 2) {
+            for (uint32_t o = 1; o < across; o <<= 1) {
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    const TileSum t{__shfl_xor(v[k].sse, (int)o), __shfl_xor(v[k].sad, (int)o), __shfl_xor(v[k].mx, (int)o)};
+                    merge(v[k], t);
+                }
+            }
+        }
+        const bool first = MODE == 2 || (lane & (across - 1u)) == 0u;   // the tile's first lane
+        if (phases == 1u) {   // the wave has seen every row of its tiles
+            if (first) store_tiles<MODE, NV>(a, ps, f, j, seg, v);
+            continue;
+        }
+        TileSum (*buf)[2][64] = red[step++ & 1u];
+        if (first) {
+            const uint32_t slot = MODE == 2 ? lane : lane >> ps.lg;
+#pragma unroll
+            for (int k = 0; k < NV; k++) buf[wave][k][slot] = v[k];
+        }
+        __syncthreads();
+        if (ph == 0u && lane < slots) {   // the waves of the first rows add the others' tiles to their own
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                v[k] = buf[wc][k][lane];
+                for (uint32_t o = 1; o < phases; o++) merge(v[k], buf[wc + o * wa][k][lane]);
+            }
+            store_tiles<MODE, NV>(a, ps, f, j, MODE == 2 ? seg0 + lane : seg0 + (lane << ps.lg), v);
+        }
+    }
+}
+
+template <typename T, bool PLANAR>
+__global__ void __launch_bounds__(kMapBlock) frame_error_map_kernel(const MapArgs a) {
+    __shared__ TileSum red[2][kMapWaves][2][64];
+    const unsigned f = blockIdx.y;
+    HF_DBG_CHECK(f < (unsigned)a.n && f < (unsigned)kMaxErrorPairs, 260);
+    const T* __restrict__ fa = static_cast<const T*>(a.a[f]);
+    const T* __restrict__ fb = static_cast<const T*>(a.b[f]);
+    const ErrorShape& s = a.sh;
+    uint32_t step = 0;
+    for (uint32_t j = blockIdx.x; j < a.th; j += gridDim.x) {
+        const uint32_t y0 = j * a.tile, y1 = y0 + a.tile < a.rows_y ? y0 + a.tile : a.rows_y;
+        const uint32_t c0 = j * (a.tile / 2u), c1 = c0 + a.tile / 2u < s.rows_u ? c0 + a.tile / 2u : s.rows_u;
+        map_pass<T, 0, 261>(fa, fb, a, MapPass{0, 0, s.pitch_ya, s.pitch_yb, s.w_y, s.segs_y, y0, y1, s.vec_y, a.lg, 0u}, f, j, red, step);
+        if constexpr (!PLANAR) {
+            map_pass<T, 1, 263>(fa, fb, a, MapPass{s.base_ca, s.base_cb, s.pitch_ca, s.pitch_cb, s.w_c, s.segs_c, c0, c1, s.vec_c, a.lg, 1u}, f, j, red, step);
+        } else {
+            for (uint32_t ch = 0; ch < 2u; ch++) {   // V's rows follow U's
+                const MapPass ps{s.base_ca + (size_t)ch * s.rows_u * s.pitch_ca, s.base_cb + (size_t)ch * s.rows_u * s.pitch_cb, s.pitch_ca, s.pitch_cb,
+                                 s.w_c, s.segs_c, c0, c1, s.vec_c, a.lg ? a.lg - 1u : 0u, 1u + ch};
+                if constexpr (sizeof(T) == 1) {
+                    if (a.lg == 0u) { map_pass<T, 2, 265>(fa, fb, a, ps, f, j, red, step); continue; }
+                }
+                map_pass<T, 0, 263>(fa, fb, a, ps, f, j, red, step);
+            }
+        }
+    }
+}
+
+// what every pair of a launch shares and the pointer tables, into the arguments of the error kernel or of the map kernel; false: n out
+// of range, or a frame beyond 2^32 work items
+template <typename Args>
+bool fill_error_args(Args& k, int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b) {
     if (n < 1 || n > kMaxErrorPairs) return false;
     const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
-    ErrorArgs k{};
     ErrorShape& s = k.sh;
     s.w_y = (uint32_t)W;
     s.pitch_ya = (uint32_t)stride_a; s.pitch_yb = (uint32_t)stride_b;
@@ -539,13 +728,22 @@ bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool
     s.vec_y = (s.pitch_ya * bpp) % 16 == 0 && (s.pitch_yb * bpp) % 16 == 0;
     s.vec_c = s.vec_y && (s.pitch_ca * bpp) % 16 == 0 && (s.pitch_cb * bpp) % 16 == 0;
     k.n = n;
-    k.slots = slots;
     for (int i = 0; i < n; i++) {
         k.a[i] = a[i]; k.b[i] = b[i];
         if (!aligned16(a[i]) || !aligned16(b[i])) s.vec_y = s.vec_c = 0;
     }
+    return true;
+}
+
+}  // namespace
+
+bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b,
+                         FrameErrorSlot* slots, hipStream_t stream) {
+    ErrorArgs k{};
+    if (!fill_error_args(k, hdr, H, W, stride_a, stride_b, planar, n, a, b)) return false;
+    k.slots = slots;
     // around kErrMaxBlocks workgroups in the whole launch, one at least per pair
-    const size_t most = items_y > items_c ? (size_t)items_y : (size_t)items_c;
+    const size_t most = k.sh.items_y > k.sh.items_c ? (size_t)k.sh.items_y : (size_t)k.sh.items_c;
     const size_t want = most ? (most + kErrBlock - 1) / kErrBlock : 1;
     const size_t cap = (size_t)kErrMaxBlocks / (size_t)n > 0 ? (size_t)kErrMaxBlocks / (size_t)n : 1;
     const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)n);
@@ -555,6 +753,32 @@ bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool
     } else {
         if (planar) HF_LAUNCH("frame_error", (frame_error_kernel<uint8_t, true>), grid, dim3(kErrBlock), 0, stream, k);
         else        HF_LAUNCH("frame_error", (frame_error_kernel<uint8_t, false>), grid, dim3(kErrBlock), 0, stream, k);
+    }
+    return true;
+}
+
+// one map per pair into maps[i][3][th][tw]; tile 16, 32 or 64; every entry is stored by the launch
+bool launch_frame_error_map(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int tile, int n, const void* const* a,
+                            const void* const* b, void* maps, hipStream_t stream) {
+    if (tile != 16 && tile != 32 && tile != 64) return false;
+    MapArgs k{};
+    if (!fill_error_args(k, hdr, H, W, stride_a, stride_b, planar, n, a, b)) return false;
+    k.rows_y = (uint32_t)H;
+    k.tile = (uint32_t)tile;
+    const uint32_t across = (uint32_t)tile * (hdr ? 2u : 1u) / 16u;   // 1, 2, 4 or 8
+    k.lg = across >= 8 ? 3u : across >= 4 ? 2u : across >= 2 ? 1u : 0u;
+    k.tw = ((uint32_t)W + k.tile - 1) / k.tile; k.th = ((uint32_t)H + k.tile - 1) / k.tile;
+    k.entries = (size_t)n * 3u * k.th * k.tw;
+    k.maps = static_cast<TileSum*>(maps);
+    // a workgroup per band, in the order of the bands in memory; a launch of more than kMapMaxBlocks workgroups strides over them
+    const uint32_t cap = (uint32_t)kMapMaxBlocks / (uint32_t)n;
+    const dim3 grid(k.th < cap ? k.th : cap, (unsigned)n);
+    if (hdr) {
+        if (planar) HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint16_t, true>), grid, dim3(kMapBlock), 0, stream, k);
+        else        HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint16_t, false>), grid, dim3(kMapBlock), 0, stream, k);
+    } else {
+        if (planar) HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint8_t, true>), grid, dim3(kMapBlock), 0, stream, k);
+        else        HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint8_t, false>), grid, dim3(kMapBlock), 0, stream, k);
     }
     return true;
 }
@@ -723,6 +947,31 @@ int hf_frame_error(hf_ctx* c, const void* device_a, const void* device_b, int st
     if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_error: null result");
     if (int rc = enqueue_errors(c, "hf_frame_error", 1, &device_a, &device_b, stride_a, stride_b, planar, HF_ERROR_SLOTS, HF_ERROR_SLOTS + 1)) return rc;
     return read_errors(c, HF_ERROR_SLOTS, 1, HF_ERROR_SLOTS + 1, out);
+}
+
+int hf_frame_error_map_shape(const hf_ctx* c, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map) {
+    if (!c || !HF_ERROR_MAP_TILES_OK(tile)) return HF_ERR_INVALID_ARGUMENT;
+    const int tw = (c->g.W + tile - 1) / tile, th = (c->g.H + tile - 1) / tile;
+    if (tiles_x) *tiles_x = tw;
+    if (tiles_y) *tiles_y = th;
+    if (bytes_per_map) *bytes_per_map = 3 * sizeof(struct hf_error_tile) * (size_t)tw * (size_t)th;
+    return HF_OK;
+}
+
+// ordered like enqueue_errors; no slots, no memset: the launch stores every entry of the caller's buffer
+int hf_frame_error_map_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
+                               int tile, void* device_maps) {
+    const char* who = "hf_frame_error_map_enqueue";
+    HF_CHECK_CTX(c);
+    if (int rc = check_pairs(c, who, n, device_a, device_b, stride_a, stride_b, planar, 0, n, n)) return rc;
+    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
+    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    if (!hf::launch_frame_error_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, tile, n, device_a, device_b, device_maps, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
+    HF_HIP(c, hipGetLastError());
+    return HF_OK;
 }
 
 int hf_frame_ssim_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,

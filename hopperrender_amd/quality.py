@@ -1,6 +1,7 @@
 """Leave-one-out interpolation quality of a clip, measured on the device.
 
-    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--report out.json]
+    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--map 16 [--map-dir DIR]]
+                                       [--report out.json]
     python -m hopperrender_amd.quality clip.nv12 --width 1920 --height 1080 [--hdr | --pix-fmt yuv420p10le] ...
 
 Every second frame of the clip is withheld: the sources S_j = frames[2 j] go through one asynchronous context exactly as a filter would
@@ -31,11 +32,22 @@ exactly the knobs a sweep turns.  Per plane the report gains sum_loss_q32, max_l
 and the floats ssim = 1 - sum / 2^32 / count (the mean) and min_ssim = 1 - max / 2^32 (the worst window), None where there is no window;
 the clip aggregates are summed loss over summed count and the largest loss; gain_ssim_y per pair and for the clip is interpolation
 minus repeat, and clip["worst_pair_ssim"] names the pair with the lowest mean Y.  Without it the report is what it was.
+
+--map TILE / evaluate(error_map=TILE) says WHERE in the picture the error sits (TILE = 16, 32 or 64 luma pixels): behind each evaluated
+pair's error launch the per-tile map of the interpolation against the truth (hf_frame_error_map_enqueue: sse, sad, max_abs per tile and
+plane) is enqueued into one device buffer per chunk, which is read once per chunk like the sums -- 48 bytes per tile, not the frames.
+Each pair's "interpolated" dict gains "map": tile, shape [th, tw], and per plane "worst" -- the five tiles of largest sse as {x, y, sse,
+max_abs}, x and y the luma pixels of the tile's corner, ties by lower y and then lower x -- and "share_top1pct", the share of the
+plane's sse that its ceil(tiles / 100) worst tiles hold (1.0: the error is one tear; about 0.01: it is spread evenly; None where sse is
+0).  clip["worst_tile"] names pair, plane Y, x, y and sse of the worst luma tile of the clip.  --map-dir DIR / evaluate(map_dir=DIR)
+also writes one 8-bit PGM per evaluated pair (map_pair0001.pgm ...): the Y plane, one pixel per tile, sqrt(sse / count) scaled so that
+the clip's largest value is 255; that is host work on the maps already read.  Without --map none of this is called or reported.
 """
 import argparse
 import itertools
 import json
 import math
+import os
 import sys
 
 PLANES = ("Y", "U", "V")
@@ -125,17 +137,59 @@ def _add_ssim_aggregate(agg, rows, key):
         agg[p].update({"sum_loss_q32": total, "max_loss_q32": worst, "ssim_count": count}, **_ssim_floats(total, worst, count))
 
 
+def _worst_tiles(m, tile, k=5):
+    """the k tiles of largest sse of one plane's map [th][tw] (calc.frame_error_maps): ties by lower y, then lower x"""
+    import numpy as np
+    tw = m.shape[1]
+    order = np.argsort(-m["sse"].astype(np.int64).reshape(-1), kind="stable")[:k]   # (a tile's sse stays below 2^44)
+    return [{"x": int(i % tw) * tile, "y": int(i // tw) * tile, "sse": int(m["sse"].flat[i]), "max_abs": int(m["max_abs"].flat[i])} for i in order]
+
+
+def _share_top1pct(m):
+    """share of the plane's sse held by its ceil(tiles / 100) worst tiles; None where the sse is 0"""
+    sse = sorted((int(v) for v in m["sse"].flat), reverse=True)
+    total = sum(sse)
+    return None if total == 0 else sum(sse[:(len(sse) + 99) // 100]) / total
+
+
+def _map_dict(m, tile):
+    """one pair's map [3][th][tw] as the report's "map" entry"""
+    return dict({"tile": tile, "shape": [int(m.shape[1]), int(m.shape[2])]},
+                **{p: {"worst": _worst_tiles(m[i], tile), "share_top1pct": _share_top1pct(m[i])} for i, p in enumerate(PLANES)})
+
+
+def _write_map_pgms(map_dir, luma, tile, H, W):
+    """luma: [(pair, Y map [th][tw])] -> one binary PGM per pair, sqrt(sse / count) per tile scaled to the largest value of the clip"""
+    import numpy as np
+    os.makedirs(map_dir, exist_ok=True)
+    th, tw = luma[0][1].shape
+    rows = np.minimum((np.arange(th) + 1) * tile, H) - np.arange(th) * tile
+    cols = np.minimum((np.arange(tw) + 1) * tile, W) - np.arange(tw) * tile
+    rms = [np.sqrt(m["sse"].astype(np.float64) / np.outer(rows, cols)) for _, m in luma]
+    top = max(float(r.max()) for r in rms)
+    for (pair, _), r in zip(luma, rms):
+        with open(os.path.join(map_dir, f"map_pair{pair:04d}.pgm"), "wb") as f:
+            f.write(b"P5\n%d %d\n255\n" % (tw, th))
+            f.write(np.rint(r * (255.0 / top) if top > 0 else r).astype(np.uint8).tobytes())
+
+
 def _minus(a, b):
     return None if a is None or b is None else a - b
 
 
 def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
-             device_index=0, device=None, ssim=False, **settings):
+             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, **settings):
     """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
     settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
     library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
     scene-change detection would have taken per period (costs one wait per period; the outputs evaluated are always the warps).
-    ssim: also score every comparison with the device's windowed SSIM (module docstring); off, nothing of it is called or reported."""
+    ssim: also score every comparison with the device's windowed SSIM (module docstring); off, nothing of it is called or reported.
+    error_map: 16, 32 or 64 -- also the per-tile error map of every interpolation (module docstring); 0, nothing of it is called or
+    reported.  map_dir: with error_map, a directory for one PGM heat map of the Y plane per evaluated pair."""
+    if error_map not in (0, 16, 32, 64):
+        raise ValueError(f"evaluate: error_map {error_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
+    if map_dir and not error_map:
+        raise ValueError("evaluate: map_dir needs error_map")
     unknown = set(settings) - set(SETTINGS)
     if unknown:
         raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
@@ -148,6 +202,11 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
     filt = dev.scene_filter(source_frame_time, scene_threshold) if detect_scene_cuts else None
     frame_bytes, out_bytes = int(main.input_frame_bytes), int(main.output_frame_bytes)
     free_in, free_out, rows, cuts = [], [], [], []
+    maps_buf, luma_maps = None, []                  # error_map: the chunk's maps on the device; map_dir: (pair, Y map) of every pair
+    if error_map:
+        from .calc import frame_error_maps
+        tiles_x, tiles_y, map_bytes = main.frameErrorMapShape(error_map)
+        maps_buf = dev.buffer(map_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
     take = lambda pool, nbytes: pool.pop() if pool else dev.buffer(nbytes)
     src = {}    # period -> device frame of its source; the last three outlive a chunk (the context's ring still references them)
     try:
@@ -194,6 +253,8 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     main.frameErrorEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
                     if ssim:
                         main.frameSsimEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
+                    if error_map:
+                        main.frameErrorMapEnqueue([out.ptr], [truth.ptr], error_map, maps_buf.ptr + (slot // 2) * map_bytes)
                     slot += 2
                 if filt is not None:
                     main.waitFlow()
@@ -203,6 +264,9 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                                  "kind": "copy" if filt.detect(fc) else "warp"})
             got = main.frameErrorRead(0, slot) if slot else []
             got_ssim = main.frameSsimRead(0, slot) if ssim and slot else []
+            if error_map and slot:                  # (the read above has waited for the context)
+                import numpy as np
+                got_maps = frame_error_maps(maps_buf.download(np.uint8, (slot // 2) * map_bytes), slot // 2, tiles_x, tiles_y)
             for i, s in enumerate(s for s in chunk if s["evaluated"]):
                 row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
                        "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
@@ -212,6 +276,10 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     _add_ssim(row["interpolated"], got_ssim[2 * i])
                     _add_ssim(row["repeat"], got_ssim[2 * i + 1])
                     row["gain_ssim_y"] = _minus(row["interpolated"]["Y"]["ssim"], row["repeat"]["Y"]["ssim"])
+                if error_map:
+                    row["interpolated"]["map"] = _map_dict(got_maps[i], error_map)
+                    if map_dir:
+                        luma_maps.append((s["pair"], got_maps[i][0].copy()))
                 rows.append(row)
             # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
             last = chunk[-1]["period"]
@@ -222,7 +290,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         aux.close()
         if filt is not None:
             filt.close()
-        for b in free_in + free_out + list(src.values()):
+        for b in free_in + free_out + list(src.values()) + ([maps_buf] if maps_buf is not None else []):
             b.free()
     worst = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["psnr"] is None else r["interpolated"]["Y"]["psnr"])
     clip = {"interpolated": _aggregate(rows, "interpolated", peak), "repeat": _aggregate(rows, "repeat", peak),
@@ -235,6 +303,12 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         clip["gain_ssim_y"] = _minus(clip["interpolated"]["Y"]["ssim"], clip["repeat"]["Y"]["ssim"])
         low = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["ssim"] is None else r["interpolated"]["Y"]["ssim"])
         clip["worst_pair_ssim"] = {"pair": low["pair"], "ssim_y": low["interpolated"]["Y"]["ssim"]}
+    if error_map:
+        top = max(rows, key=lambda r: r["interpolated"]["map"]["Y"]["worst"][0]["sse"])   # (the first of equals: the earlier pair)
+        t = top["interpolated"]["map"]["Y"]["worst"][0]
+        clip["worst_tile"] = {"pair": top["pair"], "plane": "Y", "x": t["x"], "y": t["y"], "sse": t["sse"]}
+        if map_dir:
+            _write_map_pgms(map_dir, luma_maps, error_map, H, W)
     return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
             "settings": dict(st, black_level=float(black), white_level=float(white)),
             "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
@@ -305,6 +379,10 @@ def parse_args(argv=None):
                     help="evaluate every value of a knob (radius, delta, neighbor, blur, iterations, max-calc-res); repeatable: the cartesian product")
     ap.add_argument("--ssim", action="store_true",
                     help="also score every comparison with the windowed SSIM (8 x 8 windows at stride 4): mean and worst window per plane")
+    ap.add_argument("--map", type=int, default=0, choices=(0, 16, 32, 64), metavar="TILE",
+                    help="also locate the error: per-tile error maps of every interpolation, tiles of 16, 32 or 64 luma pixels")
+    ap.add_argument("--map-dir", default=None, metavar="DIR",
+                    help="with --map: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
     ap.add_argument("--report", default=None, help="write the reports as JSON")
     a = ap.parse_args(argv)
     if a.pix_fmt is None:
@@ -313,6 +391,8 @@ def parse_args(argv=None):
         a.hdr = True
     elif a.hdr:
         ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
+    if a.map_dir and not a.map:
+        ap.error("--map-dir needs --map TILE")
     try:
         a.sweeps = parse_sweeps(a.sweep)
     except ValueError as e:
@@ -337,11 +417,12 @@ def main(argv=None, device=None):
     base = {"search_radius": a.radius, "delta_scalar": a.delta, "neighbor_scalar": a.neighbor, "blur_radius": a.blur,
             "iterations": a.iterations, "max_calc_res": a.max_calc_res}
     reports = []
-    for sweep in a.sweeps:
+    for k, sweep in enumerate(a.sweeps):
         st = dict(base, **sweep)
+        map_dir = a.map_dir and (os.path.join(a.map_dir, f"setting{k:02d}") if len(a.sweeps) > 1 else a.map_dir)
         rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
                        scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
-                       device=device, ssim=a.ssim, **st)
+                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, **st)
         reports.append(rep)
         c = rep["clip"]
         knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
@@ -350,7 +431,8 @@ def main(argv=None, device=None):
               f"worst pair {c['worst_pair']['pair']} ({_db(c['worst_pair']['psnr_y'])} dB)" + (
                   f"  SSIM Y/U/V {_ss(c['interpolated']['Y']['ssim'])} {_ss(c['interpolated']['U']['ssim'])} {_ss(c['interpolated']['V']['ssim'])}  "
                   f"repeat Y {_ss(c['repeat']['Y']['ssim'])}  worst window {_ss(c['interpolated']['Y']['min_ssim'])}  "
-                  f"worst pair {c['worst_pair_ssim']['pair']} ({_ss(c['worst_pair_ssim']['ssim_y'])})" if a.ssim else ""))
+                  f"worst pair {c['worst_pair_ssim']['pair']} ({_ss(c['worst_pair_ssim']['ssim_y'])})" if a.ssim else "") + (
+                  f"  worst tile pair {c['worst_tile']['pair']} at ({c['worst_tile']['x']}, {c['worst_tile']['y']}) sse {c['worst_tile']['sse']}" if a.map else ""))
     if a.report:
         with open(a.report, "w") as f:
             json.dump({"input": a.input, "reports": reports}, f, indent=1)

@@ -393,6 +393,34 @@ int hf_frame_error_read(hf_ctx* ctx, int first_slot, int n, struct hf_frame_erro
 int hf_frame_error(hf_ctx* ctx, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar,
                    struct hf_frame_error* out);
 
+/* ---- Per-tile frame error maps on the device: WHERE two frames are apart ----
+ * The error sums above reduce a frame to a few numbers per plane; a map keeps them per tile, so that a quality sweep or a parity test
+ * learns where the error sits (a moving edge, the frame border, one flow window) without reading either frame back.  The pairs,
+ * strides, layouts, planes and compared columns are those of hf_frame_error_enqueue (padding columns are never read); step by step:
+ *   1. Tiles.  `tile` is the tile edge in luma pixels, 16, 32 or 64 (HF_ERROR_MAP_TILES_OK);  tw = (frame_width + tile - 1) / tile,
+ *      th = (frame_height + tile - 1) / tile.
+ *   2. Y, tile (i, j) covers rows [j tile, min((j + 1) tile, frame_height)) and columns [i tile, min((i + 1) tile, frame_width)).
+ *      U and V, tile (i, j) covers chroma rows [j tile / 2, min((j + 1) tile / 2, frame_height / 2)) and chroma columns
+ *      [i tile / 2, min((i + 1) tile / 2, frame_width / 2)) of that channel: the same picture area as the Y tile.
+ *   3. Per tile, over its elements, in integers:  sse = sum (a - b)^2,  sad = sum |a - b|,  max_abs = max |a - b|  (a 64 x 64 tile of
+ *      16-bit elements stays below 2^44 in sse and 2^28 in sad).
+ *   4. One map is `struct hf_error_tile [3][th][tw]`, plane 0 Y, 1 U, 2 V: bytes_per_map = 48 tw th.  device_maps is ONE caller-owned
+ *      device buffer of n bytes_per_map bytes, 16-byte aligned; the map of pair i starts at byte i bytes_per_map.  (One buffer, not a
+ *      table of pointers: the tables of a and b take 3 KB of the 4 KB of kernel arguments at HF_MAX_ERROR_PAIRS already.)
+ *   5. EVERY entry of every map is written by the launch, zeros included: the caller does not clear the buffer.  Per pair and plane
+ *      the sum of sse over the tiles is hf_frame_error's sse, the sum of sad its sad, the largest max_abs its max_abs.
+ *   hf_frame_error_map_shape    tw, th and bytes_per_map of ctx's geometry for a tile (any of the three results may be NULL).
+ *   hf_frame_error_map_enqueue  only enqueues, ordered exactly like hf_frame_error_enqueue (behind every warp, copy and update of ctx,
+ *                               the warp stream of an HF_FLAG_DUAL_STREAM context included; a batch member on its batch's stream).
+ *                               Read the maps with hf_memcpy_d2h after hf_sync.  The frames must stay as they are until it has run.
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued: everything hf_frame_error_enqueue refuses but the slot range (there are no slots), a
+ * tile outside {16, 32, 64}, a NULL or misaligned device_maps.  Additive to ABI version 6. */
+#define HF_ERROR_MAP_TILES_OK(t) ((t) == 16 || (t) == 32 || (t) == 64)
+struct hf_error_tile { uint64_t sse; uint32_t sad; uint32_t max_abs; };   /* 16 bytes */
+int hf_frame_error_map_shape(const hf_ctx* ctx, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map);
+int hf_frame_error_map_enqueue(hf_ctx* ctx, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b,
+                               int planar, int tile, void* device_maps);
+
 /* ---- Windowed SSIM on the device, beside the frame error sums ----
  * PSNR rewards smoothing (a ghost of two averaged frames scores above a sharp, slightly misplaced edge) and cannot tell a frame that is
  * a little wrong everywhere from one torn in a single place; structural similarity over small windows is the usual second judge, as a
