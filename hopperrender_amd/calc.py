@@ -252,6 +252,26 @@ class OpticalFlowCalc:
                                            int(stride_b) or self.m_frameWidth, 1 if planar else 0, int(peak), C.byref(e)), self._ctx)
         return self._frame_ssim_dict(e)
 
+    # ---- per-tile SSIM maps on the device (hf_frame_ssim_map*) ----
+    def frameSsimMapShape(self, tile):
+        """hf_frame_ssim_map_shape: (tiles_x, tiles_y, bytes of one map) of this context's geometry for tiles of `tile` luma pixels: the
+        tile grid of frameErrorMapShape, 72 bytes a tile."""
+        tw, th, nbytes = C.c_int(), C.c_int(), C.c_size_t()
+        capi.check(self._lib.hf_frame_ssim_map_shape(self._ctx, int(tile), C.byref(tw), C.byref(th), C.byref(nbytes)), self._ctx)
+        return tw.value, th.value, nbytes.value
+
+    def frameSsimMapEnqueue(self, a_ptrs, b_ptrs, tile, maps_ptr, stride_a=0, stride_b=0, planar=False, peak=0):
+        """hf_frame_ssim_map_enqueue: the windowed SSIM of device frames a_ptrs[i] against b_ptrs[i] per tile into map i of the device
+        buffer at maps_ptr (len(a_ptrs) maps of frameSsimMapShape(tile)[2] bytes, 16-byte aligned), behind everything this context has
+        enqueued; only enqueues.  Download the buffer after sync() and view it with frame_ssim_maps()."""
+        n = len(a_ptrs)
+        if len(b_ptrs) != n:
+            raise ValueError("frameSsimMapEnqueue: as many b frames as a frames")
+        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
+        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
+        capi.check(self._lib.hf_frame_ssim_map_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
+                                                       1 if planar else 0, int(peak), int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
+
     def setOutputBuffer(self, dev_ptr):
         capi.check(self._lib.hf_set_output_buffer(self._ctx, C.c_void_p(dev_ptr or 0)), self._ctx)
 
@@ -361,6 +381,19 @@ def frame_error_maps(raw, n, tiles_x, tiles_y):
     if a.size < need:
         raise ValueError(f"frame_error_maps: {a.size} bytes, {n} maps of 3 x {tiles_y} x {tiles_x} tiles need {need}")
     return a[:need].view(ERROR_TILE_DTYPE).reshape(n, 3, tiles_y, tiles_x)
+
+
+SSIM_TILE_DTYPE = np.dtype([("sum_loss_q32", "<u8"), ("max_loss_q32", "<u8"), ("count", "<u4"), ("reserved", "<u4")])   # struct hf_ssim_tile
+
+
+def frame_ssim_maps(raw, n, tiles_x, tiles_y):
+    """A downloaded map buffer of hf_frame_ssim_map_enqueue (bytes, or any array of n * 72 * tiles_y * tiles_x bytes) as a structured
+    array [n][3][tiles_y][tiles_x] with fields sum_loss_q32, max_loss_q32, count, reserved; plane 0 Y, 1 U, 2 V.  A view, no copy."""
+    a = np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw).reshape(-1).view(np.uint8)
+    need = n * 3 * tiles_y * tiles_x * SSIM_TILE_DTYPE.itemsize
+    if a.size < need:
+        raise ValueError(f"frame_ssim_maps: {a.size} bytes, {n} maps of 3 x {tiles_y} x {tiles_x} tiles need {need}")
+    return a[:need].view(SSIM_TILE_DTYPE).reshape(n, 3, tiles_y, tiles_x)
 
 
 class DeviceBuffer:

@@ -99,6 +99,11 @@ class HfFrameSsim(C.Structure):
     _fields_ = [("sum_loss_q32", C.c_uint64 * 3), ("max_loss_q32", C.c_uint64 * 3), ("count", C.c_uint64 * 3)]
 
 
+class HfSsimTile(C.Structure):
+    """struct hf_ssim_tile: summed and largest window loss and window count of one tile of one plane (hf_frame_ssim_map_enqueue), 24 bytes"""
+    _fields_ = [("sum_loss_q32", C.c_uint64), ("max_loss_q32", C.c_uint64), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class HfErrorTile(C.Structure):
     """struct hf_error_tile: the integer error sums of one tile of one plane (hf_frame_error_map_enqueue), 16 bytes"""
     _fields_ = [("sse", C.c_uint64), ("sad", C.c_uint32), ("max_abs", C.c_uint32)]
@@ -191,6 +196,8 @@ SIGNATURES = {
     "hf_frame_ssim_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "hf_frame_ssim_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameSsim)]),
     "hf_frame_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(HfFrameSsim)]),
+    "hf_frame_ssim_map_shape": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)]),
+    "hf_frame_ssim_map_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp]),
     "hf_download_frame_device": (_i, [_vp, _vp]),
     "hf_set_output_buffer": (_i, [_vp, _vp]),
     "hf_sync": (_i, [_vp]),

@@ -213,6 +213,11 @@ struct FrameSsimSlot {
 };
 bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int n, const void* const* a,
                        const void* const* b, FrameSsimSlot* slots, hipStream_t stream);
+// Per-tile SSIM maps (hf_metrics.hip; hf_frame_ssim_map*): the same pairs, strides, layouts and constants as launch_frame_ssim, the tile
+// grid of launch_frame_error_map; maps = n maps of hf_ssim_tile [3][th][tw] in one device buffer, every entry of which the launch
+// stores (no memset, no atomics).  false: nothing launched (n or tile out of range).
+bool launch_frame_ssim_map(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int tile, int n,
+                           const void* const* a, const void* const* b, void* maps, hipStream_t stream);
 bool dbg_bounds_read_metrics(unsigned out[5], bool reset);
 // Scene-cut copy periods of a batch, decided on the device (hf_scene.hip; hf_batch_run_period_auto).  One record per member and period:
 // the layout of hf_scene_record (include/hopperflow.h).

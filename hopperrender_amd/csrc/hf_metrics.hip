@@ -702,6 +702,263 @@ __global__ void __launch_bounds__(kMapBlock) frame_error_map_kernel(const MapArg
     }
 }
 
+// ---- Per-tile SSIM maps (hf_frame_ssim_map*; the definition is in include/hopperflow.h) ----
+// The windowed SSIM above kept per tile of the error maps' grid: one hf_ssim_tile {sum_loss_q32, max_loss_q32, count} per tile and plane,
+// in one caller-owned buffer for all pairs of the launch.  A window belongs to the tile that holds its first block.  Same pointer table,
+// layouts, pitches, unit (16 bytes of four rows on each side), block sums and window loss as the SSIM kernel, whose SsimPlane, SsimBlk,
+// SsimWide, ssim_add_row, ssim_wide, SsimRows and ssim_loss it uses as they are.
+//
+// The mapping.  A PATCH is what a workgroup takes at a time: kSmapRows = 16 block rows of windows by pu units of windows, and one block
+// row and one unit of halo behind them (read again by the neighbouring patch: 17 / 16 x (pu + 1) / pu = 1.10 of the frame, as in the
+// SSIM kernel).  16 block rows are a whole number of tile rows for every tile (a tile is tb = 2 .. 16 blocks down), and pu is the largest
+// multiple of the units a tile is across (tu = 1, 2, 4 or 8) that leaves (pu + 1) x 17 positions within two per lane: 29, 28, 28 or 24.
+// So a tile lies whole inside ONE patch and patches start at tile corners: nothing is exchanged between workgroups, every entry is
+// stored once by the workgroup that owns it -- no atomics, no memset.  Per patch:
+//     0. / 1.  as in the SSIM kernel: the wide loads of the NEXT patch are issued ahead of the windows of this one; block sums into LDS;
+//     2. behind a barrier: every position that owns windows (neither halo) scores the windows of its unit and leaves their summed and
+//        largest loss in LDS -- as ONE value (the unit lies in one tile), or two: U and V of an interleaved row, or the two halves of a
+//        unit that holds two tiles (8-bit planar chroma at tile 16, a tile 2 blocks across and the unit 4);
+//     3. behind a second barrier: lanes in rows of 32 (lane = unit, row = value and tile row of the patch; two rounds where there are more
+//        than 8) add the tb positions below each other, the tu lanes of a tile meet in xor-shuffles, the tile's first lane stores the
+//        24-byte entry -- neighbouring tiles, neighbouring stores.  count is not summed: a tile's windows follow from bw, bh and tb.
+// Losses are integers up to 2^33 and a tile has at most 256 windows, so doubles carry sum and maximum exactly (SsimLane).
+// Patches are numbered through the planes of a frame and a workgroup strides over them; every plane has at least one patch (a plane
+// without a window still has entries, all zero), and tiles past the plane's last window come out of step 3 as zeros.
+// LDS: 17 x 4 x 30 blocks of 16 bytes (8 bit; 17 x 2 x 30 of 24 bytes at 16 bit) + 16 x 2 x 32 values of 16 bytes = 48 / 40 KB.
+constexpr int kSmapBlock = 256;
+constexpr int kSmapRows = 16;       // block rows of windows a patch owns
+constexpr int kSmapWidth = 30;      // units of a patch at the most, halo included
+constexpr int kSmapOwn = kSmapWidth - 1;
+static_assert(kSmapWidth * (kSmapRows + 1) <= kSsimPerLane * kSmapBlock, "a patch is two positions per lane");
+static_assert(kSmapOwn <= 32, "step 3: a lane per unit in rows of 32");
+
+struct SsimTileOut {     // the layout of hf_ssim_tile
+    unsigned long long sum, mx;
+    uint32_t cnt, reserved;
+};
+static_assert(sizeof(SsimTileOut) == sizeof(struct hf_ssim_tile) && offsetof(SsimTileOut, mx) == offsetof(struct hf_ssim_tile, max_loss_q32) &&
+              offsetof(SsimTileOut, cnt) == offsetof(struct hf_ssim_tile, count), "SsimTileOut is hf_ssim_tile");
+
+struct SmapPlane {
+    SsimPlane p;                     // (tiles_x, tile_first: patches across, number of the plane's first patch)
+    uint32_t pu;                     // units of windows a patch owns
+    uint32_t tb, lg_tb;              // tile edge in blocks, 2^lg_tb
+    uint32_t lg_tu;                  // a tile is 2^lg_tu units across ...
+    uint32_t halves;                 // ... or half a unit
+};
+struct SmapArgs {
+    SmapPlane pl[3];                 // luma; interleaved UV, or U and V
+    uint32_t patches;
+    uint32_t tw, th;
+    int n;
+    size_t elems_a, elems_b;         // extent of a frame of side a / b (debug-bounds)
+    size_t entries;                  // n 3 th tw (debug-bounds)
+    long long c1, c2;
+    SsimTileOut* maps;               // [n][3][th][tw]
+    const void* a[kMaxErrorPairs];
+    const void* b[kMaxErrorPairs];
+};
+static_assert(sizeof(SmapArgs) <= 4096, "kernel arguments: 4 KB");
+
+struct SmapAt {          // where a patch lies: plane, first unit, first block row
+    uint32_t pl, u0, j0;
+};
+template <bool PLANAR>
+__device__ __forceinline__ SmapAt smap_locate(const SmapArgs& a, uint32_t t) {
+    const uint32_t pl = t < a.pl[1].p.tile_first ? 0u : (!PLANAR || t < a.pl[2].p.tile_first) ? 1u : 2u;
+    const uint32_t l = t - a.pl[pl].p.tile_first, py = l / a.pl[pl].p.tiles_x;
+    return SmapAt{pl, (l - py * a.pl[pl].p.tiles_x) * a.pl[pl].pu, py * (uint32_t)kSmapRows};
+}
+struct SmapPos {         // a lane's two positions (unit, block row) within a patch pw units wide; lr > kSmapRows: none
+    uint32_t lu[kSsimPerLane], lr[kSsimPerLane];
+};
+__device__ __forceinline__ SmapPos smap_pos(uint32_t pw) {
+    SmapPos ps;
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t it = threadIdx.x + n * kSmapBlock;
+        ps.lr[n] = it / pw; ps.lu[n] = it - ps.lr[n] * pw;
+    }
+    return ps;
+}
+struct SmapPart {        // the windows of one position in one tile: summed and largest loss
+    double sum, mx;
+};
+
+// step 0 of a patch: issue its wide loads
+template <typename T>
+__device__ __forceinline__ void smap_fetch(const T* __restrict__ fa, const T* __restrict__ fb, const SmapArgs& a, const SsimPlane& p,
+                                           const SmapAt& at, const SmapPos& ps, SsimRows& rows) {
+    constexpr uint32_t EL = 16 / sizeof(T);
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t u = at.u0 + ps.lu[n], j = at.j0 + ps.lr[n];
+        if (ps.lr[n] > (uint32_t)kSmapRows || !ssim_wide<T>(p, u, j)) continue;
+#pragma unroll
+        for (uint32_t r = 0; r < 4; r++) {
+            const size_t ia = p.base_a + (size_t)(4u * j + r) * p.pitch_a + u * EL, ib = p.base_b + (size_t)(4u * j + r) * p.pitch_b + u * EL;
+            HF_DBG_CHECK(ia + EL <= a.elems_a && ib + EL <= a.elems_b && u * EL + EL <= p.w_row, 271);
+            rows.a[n][r] = *reinterpret_cast<const uint4*>(fa + ia); rows.b[n][r] = *reinterpret_cast<const uint4*>(fb + ib);
+        }
+    }
+}
+
+// step 1: the block sums of the patch into LDS (ssim_sums with the patch's geometry)
+template <typename T, int CH>
+__device__ __forceinline__ void smap_sums(const T* __restrict__ fa, const T* __restrict__ fb, const SmapArgs& a, const SsimPlane& p,
+                                          const SmapAt& at, const SmapPos& ps, const SsimRows& rows, SsimBlk<T> (*lds)[4 / sizeof(T)][kSmapWidth]) {
+    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
+        if (lr > (uint32_t)kSmapRows || j >= p.bh || u * BPU >= p.bw) continue;
+        SsimBlk<T> blk[NB] = {};
+        if (ssim_wide<T>(p, u, j)) {
+            SsimWide<T> w[NB];
+#pragma unroll
+            for (uint32_t r = 0; r < 4; r++) ssim_add_row<T, CH>(w, rows.a[n][r], rows.b[n][r]);
+#pragma unroll
+            for (uint32_t k = 0; k < NB; k++) blk[k] = w[k].finish();
+        } else {
+            const size_t oa = p.base_a + (size_t)(4u * j) * p.pitch_a, ob = p.base_b + (size_t)(4u * j) * p.pitch_b;
+#pragma unroll
+            for (uint32_t c = 0; c < (uint32_t)CH; c++)
+#pragma unroll
+                for (uint32_t k = 0; k < BPU; k++) {
+                    const uint32_t i = u * BPU + k;
+                    if (i >= p.bw) continue;   // (a unit past the last whole block of the row: nothing of it is read)
+                    for (uint32_t r = 0; r < 4; r++)
+                        for (uint32_t e = 0; e < 4; e++) {
+                            const uint32_t x = (4u * i + e) * CH + c;
+                            const size_t ia = oa + (size_t)r * p.pitch_a + x, ib = ob + (size_t)r * p.pitch_b + x;
+                            HF_DBG_CHECK(x < p.w_row && ia < a.elems_a && ib < a.elems_b, 272);
+                            blk[c * BPU + k].add1(fa[ia], fb[ib]);
+                        }
+                }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < NB; k++) lds[lr][k][lu] = blk[k];
+    }
+}
+
+// step 2, behind a barrier: the windows of every position that owns some, per position into part[block row][value][unit]
+template <typename T, int CH>
+__device__ __forceinline__ void smap_windows(const SmapArgs& a, const SmapPlane& m, const SmapAt& at, const SmapPos& ps,
+                                             const SsimBlk<T> (*lds)[4 / sizeof(T)][kSmapWidth], SmapPart (*part)[2][32]) {
+    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
+    const SsimPlane& p = m.p;
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
+        if (lu >= m.pu || lr >= (uint32_t)kSmapRows) continue;   // halo: its windows are the next patch's
+        SmapPart v[2] = {{0.0, 0.0}, {0.0, 0.0}};
+        if (j + 1 < p.bh && u * BPU + 1 < p.bw) {
+#pragma unroll
+            for (uint32_t c = 0; c < (uint32_t)CH; c++) {
+                SsimBlk<T> col[BPU + 1];   // blocks (i, j) + (i, j + 1) of the unit's blocks and of the first one to the right
+#pragma unroll
+                for (uint32_t k = 0; k < BPU; k++) col[k] = lds[lr][c * BPU + k][lu] + lds[lr + 1][c * BPU + k][lu];
+                col[BPU] = lds[lr][c * BPU][lu + 1] + lds[lr + 1][c * BPU][lu + 1];   // (never written where no block is: then no window uses it)
+#pragma unroll
+                for (uint32_t k = 0; k < BPU; k++) {
+                    if (u * BPU + k + 1 >= p.bw) continue;
+                    const double loss = ssim_loss<T>(col[k] + col[k + 1], a.c1, a.c2);
+                    const bool second = CH == 2 ? c == 1u : (BPU == 4 && k >= 2u && m.halves);
+                    SmapPart& t = v[second ? 1 : 0];
+                    t.sum += loss; t.mx = fmax(t.mx, loss);
+                }
+            }
+        }
+        part[lr][0][lu] = v[0]; part[lr][1][lu] = v[1];
+    }
+}
+
+// N positions below each other in part[][value][unit]
+template <int N>
+__device__ __forceinline__ void smap_column(const SmapPart* col, double& sum, double& mx) {
+    constexpr int G = N < 4 ? N : 4;   // reads in flight at once (16 registers: more would cost the 16-bit kernels a wave per SIMD)
+#pragma unroll 1
+    for (int r0 = 0; r0 < N; r0 += G) {
+        SmapPart v[G];
+#pragma unroll
+        for (int r = 0; r < G; r++) v[r] = col[(r0 + r) * 2 * 32];
+#pragma unroll
+        for (int r = 0; r < G; r++) { sum += v[r].sum; mx = fmax(mx, v[r].mx); }
+    }
+}
+
+// step 3, behind a second barrier: the tiles of the patch out of part[][][] into the pair's map
+template <int CH>
+__device__ __forceinline__ void smap_store(const SmapArgs& a, const SmapPlane& m, const SmapAt& at, unsigned f, const SmapPart (*part)[2][32]) {
+    const uint32_t lu = threadIdx.x & 31u, g = threadIdx.x >> 5;
+    const uint32_t two = (CH == 2 || m.halves) ? 1u : 0u;                       // two values per position
+    const uint32_t combos = ((uint32_t)kSmapRows >> m.lg_tb) << two;                // (value, tile row of the patch)
+    const uint32_t tu = 1u << m.lg_tu;
+    for (uint32_t c0 = 0; c0 < combos; c0 += (uint32_t)kSmapBlock / 32u) {      // (uniform: the shuffles below are met by every lane)
+        const uint32_t cb = c0 + g, k = two ? cb & 1u : 0u, tr = cb >> two;
+        const bool live = cb < combos && lu < m.pu;
+        double sum = 0.0, mx = 0.0;
+        if (live) {   // the tb positions below each other, all reads in flight at once
+            const SmapPart* col = &part[tr << m.lg_tb][k][lu];
+            switch (m.lg_tb) {
+                case 1: smap_column<2>(col, sum, mx); break;
+                case 2: smap_column<4>(col, sum, mx); break;
+                case 3: smap_column<8>(col, sum, mx); break;
+                default: smap_column<16>(col, sum, mx); break;
+            }
+        }
+        if (!m.halves)
+            for (uint32_t o = 1; o < tu; o <<= 1) { sum += __shfl_xor(sum, (int)o); mx = fmax(mx, __shfl_xor(mx, (int)o)); }
+        if (!live || (!m.halves && (lu & (tu - 1u)))) continue;
+        const uint32_t tx = m.halves ? 2u * (at.u0 + lu) + k : (at.u0 + lu) >> m.lg_tu, ty = (at.j0 >> m.lg_tb) + tr;
+        const uint32_t pl = CH == 2 ? at.pl + k : at.pl;
+        if (tx >= a.tw || ty >= a.th) continue;
+        // the tile's windows: first blocks [tx tb, (tx + 1) tb) x [ty tb, (ty + 1) tb) among [0, bw - 1) x [0, bh - 1)
+        const int tb = (int)m.tb, left = (int)m.p.bw - 1 - (int)(tx * m.tb), below = (int)m.p.bh - 1 - (int)(ty * m.tb);
+        const int nx = left < 0 ? 0 : left < tb ? left : tb, ny = below < 0 ? 0 : below < tb ? below : tb;
+        const size_t e = (((size_t)f * 3u + pl) * a.th + ty) * a.tw + tx;
+        HF_DBG_CHECK(e < a.entries && pl < 3u, 273);
+        unsigned long long* out = reinterpret_cast<unsigned long long*>(a.maps + e);
+        out[0] = (unsigned long long)sum; out[1] = (unsigned long long)mx; out[2] = (unsigned long long)(uint32_t)(nx * ny);
+    }
+}
+
+template <typename T, bool PLANAR>
+__global__ void __launch_bounds__(kSmapBlock) frame_ssim_map_kernel(const SmapArgs a) {
+    __shared__ SsimBlk<T> lds[kSmapRows + 1][4 / sizeof(T)][kSmapWidth];
+    __shared__ SmapPart part[kSmapRows][2][32];
+    const unsigned f = blockIdx.y;
+    HF_DBG_CHECK(f < (unsigned)a.n && f < (unsigned)kMaxErrorPairs, 270);
+    const T* __restrict__ fa = static_cast<const T*>(a.a[f]);
+    const T* __restrict__ fb = static_cast<const T*>(a.b[f]);
+    SsimRows rows = {};
+    uint32_t t = blockIdx.x;
+    SmapAt at = {0, 0, 0};
+    SmapPos ps = {};
+    if (t < a.patches) { at = smap_locate<PLANAR>(a, t); ps = smap_pos(a.pl[at.pl].pu + 1u); smap_fetch<T>(fa, fb, a, a.pl[at.pl].p, at, ps, rows); }
+    while (t < a.patches) {
+        const SmapPlane& m = a.pl[at.pl];
+        const bool uv = !PLANAR && at.pl != 0;   // an interleaved UV plane: two channels
+        if (uv) smap_sums<T, 2>(fa, fb, a, m.p, at, ps, rows, lds);
+        else    smap_sums<T, 1>(fa, fb, a, m.p, at, ps, rows, lds);
+        __syncthreads();
+        const uint32_t tn = t + gridDim.x;
+        SmapAt nx = at;
+        SmapPos pn = ps;
+        if (tn < a.patches) {
+            nx = smap_locate<PLANAR>(a, tn);
+            if (a.pl[nx.pl].pu != m.pu) pn = smap_pos(a.pl[nx.pl].pu + 1u);
+            smap_fetch<T>(fa, fb, a, a.pl[nx.pl].p, nx, pn, rows);
+        }
+        if (uv) smap_windows<T, 2>(a, m, at, ps, lds, part);
+        else    smap_windows<T, 1>(a, m, at, ps, lds, part);
+        __syncthreads();   // the next patch overwrites the blocks; its windows, behind its own barrier, the values
+        if (uv) smap_store<2>(a, m, at, f, part);
+        else    smap_store<1>(a, m, at, f, part);
+        t = tn; at = nx; ps = pn;
+    }
+}
+
 // what every pair of a launch shares and the pointer tables, into the arguments of the error kernel or of the map kernel; false: n out
 // of range, or a frame beyond 2^32 work items
 template <typename Args>
@@ -840,6 +1097,71 @@ bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool p
     return true;
 }
 
+// one SSIM map per pair into maps[i][3][th][tw] of hf_ssim_tile; tile 16, 32 or 64; every entry is stored by the launch
+bool launch_frame_ssim_map(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int tile, int n,
+                           const void* const* a, const void* const* b, void* maps, hipStream_t stream) {
+    if (n < 1 || n > kMaxErrorPairs || (tile != 16 && tile != 32 && tile != 64)) return false;
+    const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
+    SmapArgs k{};
+    k.tw = ((uint32_t)W + (uint32_t)tile - 1) / (uint32_t)tile; k.th = ((uint32_t)H + (uint32_t)tile - 1) / (uint32_t)tile;
+    const uint32_t hc = (uint32_t)(H / 2), wc = (uint32_t)(W / 2);
+    const uint32_t pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a, pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
+    // wide accesses: as for the error sums (the chroma bases are whole numbers of rows behind the frame's)
+    int vec_y = ((uint32_t)stride_a * bpp) % 16 == 0 && ((uint32_t)stride_b * bpp) % 16 == 0;
+    for (int i = 0; i < n; i++) {
+        k.a[i] = a[i]; k.b[i] = b[i];
+        if (!aligned16(a[i]) || !aligned16(b[i])) vec_y = 0;
+    }
+    const int vec_c = vec_y && (pitch_ca * bpp) % 16 == 0 && (pitch_cb * bpp) % 16 == 0;
+    auto plane = [&](SmapPlane& m, uint32_t w, uint32_t h, uint32_t ch, uint32_t te, size_t base_a, size_t base_b, uint32_t pitch_a, uint32_t pitch_b, int vec) {
+        SsimPlane& p = m.p;
+        p.bw = w >> 2; p.bh = h >> 2; p.w_row = w * ch;
+        p.pitch_a = pitch_a; p.pitch_b = pitch_b; p.base_a = base_a; p.base_b = base_b; p.vec = vec;
+        const uint32_t bpu = EL / 4 / ch;                   // blocks of a channel in a unit: 1, 2 or 4
+        m.tb = te / 4;                                      // 2 .. 16
+        m.lg_tb = m.tb >= 16 ? 4u : m.tb >= 8 ? 3u : m.tb >= 4 ? 2u : 1u;
+        m.halves = m.tb < bpu;                              // (tb 2, bpu 4)
+        const uint32_t tu = m.halves ? 1u : m.tb / bpu;     // 1, 2, 4 or 8
+        m.lg_tu = tu >= 8 ? 3u : tu >= 4 ? 2u : tu >= 2 ? 1u : 0u;
+        m.pu = (uint32_t)kSmapOwn / tu * tu;
+        const uint32_t tiles_across = m.halves ? 2u * m.pu : m.pu / tu, tiles_down = (uint32_t)kSmapRows / m.tb;
+        p.tiles_x = (k.tw + tiles_across - 1) / tiles_across;
+        p.tile_first = k.patches;
+        k.patches += p.tiles_x * ((k.th + tiles_down - 1) / tiles_down);
+    };
+    const size_t base_ca = (size_t)H * (size_t)stride_a, base_cb = (size_t)H * (size_t)stride_b;
+    const uint32_t te = (uint32_t)tile;
+    plane(k.pl[0], (uint32_t)W, (uint32_t)H, 1, te, 0, 0, (uint32_t)stride_a, (uint32_t)stride_b, vec_y);
+    if (planar) {
+        plane(k.pl[1], wc, hc, 1, te / 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
+        plane(k.pl[2], wc, hc, 1, te / 2, base_ca + (size_t)hc * pitch_ca, base_cb + (size_t)hc * pitch_cb, pitch_ca, pitch_cb, vec_c);
+    } else {
+        plane(k.pl[1], wc, hc, 2, te / 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
+        k.pl[2] = k.pl[1]; k.pl[2].p.tile_first = k.patches;   // (no patch of its own: V comes with U)
+    }
+    const uint32_t rows_c = planar ? 2u * hc : hc;
+    k.elems_a = base_ca + (size_t)rows_c * pitch_ca; k.elems_b = base_cb + (size_t)rows_c * pitch_cb;
+    k.entries = (size_t)n * 3u * k.th * k.tw;
+    k.c1 = c1; k.c2 = c2;
+    k.n = n;
+    k.maps = static_cast<SsimTileOut*>(maps);
+    void (*kernel)(const SmapArgs) = hdr ? (planar ? frame_ssim_map_kernel<uint16_t, true> : frame_ssim_map_kernel<uint16_t, false>)
+                                         : (planar ? frame_ssim_map_kernel<uint8_t, true> : frame_ssim_map_kernel<uint8_t, false>);
+    // as many workgroups in the whole launch as the device holds at once, one at least per pair: a workgroup strides over its pair's patches
+    static int resident[2][2];   // by kernel; asked once (the same answer from every thread)
+    int& res = resident[hdr ? 1 : 0][planar ? 1 : 0];
+    if (!res) {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSmapBlock, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) { per_cu = 2; cus = 256; }
+        res = per_cu * cus;
+    }
+    const uint32_t cap = (uint32_t)res / (uint32_t)n > 0 ? (uint32_t)res / (uint32_t)n : 1u;
+    const dim3 grid(k.patches < cap ? k.patches : cap, (unsigned)n);
+    HF_LAUNCH("frame_ssim_map", kernel, grid, dim3(kSmapBlock), 0, stream, k);
+    return true;
+}
+
 bool dbg_bounds_read_metrics(unsigned out[5], bool reset) {
 #ifdef HF_DEBUG_BOUNDS
     unsigned rec[5] = {0, 0, 0, 0, 0};
@@ -900,15 +1222,22 @@ static int read_errors(hf_ctx* c, int first_slot, int n, int max_slot, struct hf
     return sync_ctx(c);
 }
 
+// the peak rule and the integer constants of the SSIM calls (hopperflow.h, step 3); refuses a peak outside its range
+static int ssim_constants(hf_ctx* c, const char* who, int planar, int peak, long long* c1, long long* c2) {
+    const int top = c->g.hdr ? 65535 : 255;
+    if (peak < 0 || peak > top) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: peak %d outside 1 .. %d (0: the format's own)", who, peak, top);
+    const long long pk = peak ? peak : !c->g.hdr ? 255 : planar ? 1023 : 65535;
+    *c1 = (64 * pk * pk + 5000) / 10000; *c2 = (9 * 64 * 63 * pk * pk + 5000) / 10000;
+    return HF_OK;
+}
+
 // The windowed SSIM of the same pairs into slots of its own: ordered, refused and read like the error sums.  peak 0: the format's own.
 static int enqueue_ssim(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar, int peak,
                         int first_slot, int max_slot) {
     HF_CHECK_CTX(c);
     if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, HF_SSIM_SLOTS)) return rc;
-    const int top = c->g.hdr ? 65535 : 255;
-    if (peak < 0 || peak > top) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: peak %d outside 1 .. %d (0: the format's own)", who, peak, top);
-    const long long pk = peak ? peak : !c->g.hdr ? 255 : planar ? 1023 : 65535;
-    const long long c1 = (64 * pk * pk + 5000) / 10000, c2 = (9 * 64 * 63 * pk * pk + 5000) / 10000;
+    long long c1, c2;
+    if (int rc = ssim_constants(c, who, planar, peak, &c1, &c2)) return rc;
     if (int rc = set_device(c)) return rc;
     const bool fresh = !c->ssim_slots;
     if (fresh) HF_HIP(c, alloc_device(c->ssim_slots, (size_t)(HF_SSIM_SLOTS + 1) * sizeof(hf::FrameSsimSlot)));
@@ -986,6 +1315,33 @@ int hf_frame_ssim(hf_ctx* c, const void* device_a, const void* device_b, int str
     if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_ssim: null result");
     if (int rc = enqueue_ssim(c, "hf_frame_ssim", 1, &device_a, &device_b, stride_a, stride_b, planar, peak, HF_SSIM_SLOTS, HF_SSIM_SLOTS + 1)) return rc;
     return read_ssim(c, HF_SSIM_SLOTS, 1, HF_SSIM_SLOTS + 1, out);
+}
+
+int hf_frame_ssim_map_shape(const hf_ctx* c, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map) {
+    if (!c || !HF_ERROR_MAP_TILES_OK(tile)) return HF_ERR_INVALID_ARGUMENT;
+    const int tw = (c->g.W + tile - 1) / tile, th = (c->g.H + tile - 1) / tile;
+    if (tiles_x) *tiles_x = tw;
+    if (tiles_y) *tiles_y = th;
+    if (bytes_per_map) *bytes_per_map = 3 * sizeof(struct hf_ssim_tile) * (size_t)tw * (size_t)th;
+    return HF_OK;
+}
+
+// ordered like enqueue_errors; no slots, no memset: the launch stores every entry of the caller's buffer
+int hf_frame_ssim_map_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
+                              int peak, int tile, void* device_maps) {
+    const char* who = "hf_frame_ssim_map_enqueue";
+    HF_CHECK_CTX(c);
+    if (int rc = check_pairs(c, who, n, device_a, device_b, stride_a, stride_b, planar, 0, n, n)) return rc;
+    long long c1, c2;
+    if (int rc = ssim_constants(c, who, planar, peak, &c1, &c2)) return rc;
+    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
+    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    if (!hf::launch_frame_ssim_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, tile, n, device_a, device_b, device_maps, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
+    HF_HIP(c, hipGetLastError());
+    return HF_OK;
 }
 
 }  // extern "C"

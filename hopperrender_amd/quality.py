@@ -1,6 +1,6 @@
 """Leave-one-out interpolation quality of a clip, measured on the device.
 
-    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--map 16 [--map-dir DIR]]
+    python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--map 16] [--ssim-map 16] [--map-dir DIR]
                                        [--report out.json]
     python -m hopperrender_amd.quality clip.nv12 --width 1920 --height 1080 [--hdr | --pix-fmt yuv420p10le] ...
 
@@ -42,6 +42,19 @@ plane's sse that its ceil(tiles / 100) worst tiles hold (1.0: the error is one t
 0).  clip["worst_tile"] names pair, plane Y, x, y and sse of the worst luma tile of the clip.  --map-dir DIR / evaluate(map_dir=DIR)
 also writes one 8-bit PGM per evaluated pair (map_pair0001.pgm ...): the Y plane, one pixel per tile, sqrt(sse / count) scaled so that
 the clip's largest value is 255; that is host work on the maps already read.  Without --map none of this is called or reported.
+
+--ssim-map TILE / evaluate(ssim_map=TILE) says where the STRUCTURE is worst: the error map holds squared and absolute error, the judge
+that a ghost passes, and --ssim gives the score of the worst window but not its place.  Behind each evaluated pair's error launch the
+per-tile SSIM map of the interpolation against the truth (hf_frame_ssim_map_enqueue: summed and largest window loss and window count
+per tile and plane, a window belonging to the tile of its first element) goes into a device buffer of its own per chunk, read once per
+chunk -- 72 bytes per tile.  It is independent of --ssim and --map and uses the error map's tile grid.  Each pair's "interpolated"
+dict gains "ssim_map": tile, shape [th, tw], and per plane "worst" -- the five tiles of lowest mean SSIM (largest sum_loss_q32 / count,
+compared as integers; ties by lower y and then lower x; tiles without a window left out) as {x, y, ssim, min_ssim, sum_loss_q32,
+max_loss_q32, count}, with "sse" of the same tile beside them where --map runs at the same tile size -- and "worst_window_tile",
+{x, y, max_loss_q32} of the tile that holds the plane's worst window (None in a plane without windows).  clip["worst_tile_ssim"] names
+pair, plane Y, x, y and mean SSIM of the clip's worst luma tile.  With --map-dir one more PGM per evaluated pair (ssim_pair0001.pgm ...):
+the Y plane, one pixel per tile, round(255 min(1, sum_loss_q32 / count / 2^32)), 0 where count is 0 -- an absolute scale, so maps of
+different pairs and clips compare.  Without --ssim-map none of this is called, allocated or reported.
 """
 import argparse
 import itertools
@@ -173,23 +186,79 @@ def _write_map_pgms(map_dir, luma, tile, H, W):
             f.write(np.rint(r * (255.0 / top) if top > 0 else r).astype(np.uint8).tobytes())
 
 
+def _ssim_tile_order(m):
+    """the tiles of one plane's SSIM map [th][tw] that own a window, as (sum, count, y, x), lowest mean SSIM first: largest sum / count
+    by cross-multiplication (integers: a float quotient could order 6 / 2 and 3 / 1 either way), ties by lower y, then lower x"""
+    import functools
+    tiles = [(int(m["sum_loss_q32"][y, x]), int(m["count"][y, x]), y, x) for y in range(m.shape[0]) for x in range(m.shape[1]) if m["count"][y, x]]
+    def cmp(a, b):
+        l, r = a[0] * b[1], b[0] * a[1]
+        return -1 if l > r else 1 if l < r else (a[2:] > b[2:]) - (a[2:] < b[2:])
+    return sorted(tiles, key=functools.cmp_to_key(cmp))
+
+
+def _worst_ssim_tiles(m, tile, sse=None, k=5):
+    """the k tiles of lowest mean SSIM of one plane's SSIM map; sse: the same plane of an error map of the same tile size, or None"""
+    out = []
+    for total, count, y, x in _ssim_tile_order(m)[:k]:
+        worst = int(m["max_loss_q32"][y, x])
+        out.append(dict({"x": x * tile, "y": y * tile}, **_ssim_floats(total, worst, count), sum_loss_q32=total, max_loss_q32=worst, count=count))
+        if sse is not None:
+            out[-1]["sse"] = int(sse["sse"][y, x])
+    return out
+
+
+def _worst_window_tile(m, tile):
+    """the tile that holds the plane's largest window loss (ties by lower y, then lower x); None in a plane without a window"""
+    best = None
+    for y in range(m.shape[0]):
+        for x in range(m.shape[1]):
+            if m["count"][y, x] and (best is None or int(m["max_loss_q32"][y, x]) > best["max_loss_q32"]):
+                best = {"x": x * tile, "y": y * tile, "max_loss_q32": int(m["max_loss_q32"][y, x])}
+    return best
+
+
+def _ssim_map_dict(m, tile, err=None):
+    """one pair's SSIM map [3][th][tw] as the report's "ssim_map" entry; err: the pair's error map at the same tile size, or None"""
+    return dict({"tile": tile, "shape": [int(m.shape[1]), int(m.shape[2])]},
+                **{p: {"worst": _worst_ssim_tiles(m[i], tile, None if err is None else err[i]), "worst_window_tile": _worst_window_tile(m[i], tile)}
+                   for i, p in enumerate(PLANES)})
+
+
+def _write_ssim_pgms(map_dir, luma):
+    """luma: [(pair, Y SSIM map [th][tw])] -> one binary PGM per pair: round(255 min(1, mean loss / 2^32)) per tile, 0 without a window"""
+    import numpy as np
+    os.makedirs(map_dir, exist_ok=True)
+    for pair, m in luma:
+        th, tw = m.shape
+        cnt = m["count"].astype(np.float64)
+        loss = np.where(cnt > 0, m["sum_loss_q32"].astype(np.float64) / np.maximum(cnt, 1.0) / 4294967296.0, 0.0)
+        with open(os.path.join(map_dir, f"ssim_pair{pair:04d}.pgm"), "wb") as f:
+            f.write(b"P5\n%d %d\n255\n" % (tw, th))
+            f.write(np.rint(255.0 * np.minimum(1.0, loss)).astype(np.uint8).tobytes())
+
+
 def _minus(a, b):
     return None if a is None or b is None else a - b
 
 
 def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
-             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, **settings):
+             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, ssim_map=0, **settings):
     """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
     settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
     library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
     scene-change detection would have taken per period (costs one wait per period; the outputs evaluated are always the warps).
     ssim: also score every comparison with the device's windowed SSIM (module docstring); off, nothing of it is called or reported.
     error_map: 16, 32 or 64 -- also the per-tile error map of every interpolation (module docstring); 0, nothing of it is called or
-    reported.  map_dir: with error_map, a directory for one PGM heat map of the Y plane per evaluated pair."""
+    reported.  ssim_map: 16, 32 or 64 -- also the per-tile SSIM map of every interpolation (module docstring); 0, nothing of it is
+    called, allocated or reported.  map_dir: with error_map or ssim_map, a directory for one PGM heat map of the Y plane per evaluated
+    pair and map."""
     if error_map not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: error_map {error_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
-    if map_dir and not error_map:
-        raise ValueError("evaluate: map_dir needs error_map")
+    if ssim_map not in (0, 16, 32, 64):
+        raise ValueError(f"evaluate: ssim_map {ssim_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
+    if map_dir and not error_map and not ssim_map:
+        raise ValueError("evaluate: map_dir needs error_map or ssim_map")
     unknown = set(settings) - set(SETTINGS)
     if unknown:
         raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
@@ -207,6 +276,11 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         from .calc import frame_error_maps
         tiles_x, tiles_y, map_bytes = main.frameErrorMapShape(error_map)
         maps_buf = dev.buffer(map_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
+    smaps_buf, luma_smaps = None, []                # ssim_map: the same for the SSIM maps, in a buffer of their own
+    if ssim_map:
+        from .calc import frame_ssim_maps
+        stiles_x, stiles_y, smap_bytes = main.frameSsimMapShape(ssim_map)
+        smaps_buf = dev.buffer(smap_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
     take = lambda pool, nbytes: pool.pop() if pool else dev.buffer(nbytes)
     src = {}    # period -> device frame of its source; the last three outlive a chunk (the context's ring still references them)
     try:
@@ -255,6 +329,8 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                         main.frameSsimEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
                     if error_map:
                         main.frameErrorMapEnqueue([out.ptr], [truth.ptr], error_map, maps_buf.ptr + (slot // 2) * map_bytes)
+                    if ssim_map:
+                        main.frameSsimMapEnqueue([out.ptr], [truth.ptr], ssim_map, smaps_buf.ptr + (slot // 2) * smap_bytes)
                     slot += 2
                 if filt is not None:
                     main.waitFlow()
@@ -267,6 +343,9 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
             if error_map and slot:                  # (the read above has waited for the context)
                 import numpy as np
                 got_maps = frame_error_maps(maps_buf.download(np.uint8, (slot // 2) * map_bytes), slot // 2, tiles_x, tiles_y)
+            if ssim_map and slot:
+                import numpy as np
+                got_smaps = frame_ssim_maps(smaps_buf.download(np.uint8, (slot // 2) * smap_bytes), slot // 2, stiles_x, stiles_y)
             for i, s in enumerate(s for s in chunk if s["evaluated"]):
                 row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
                        "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
@@ -280,6 +359,10 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     row["interpolated"]["map"] = _map_dict(got_maps[i], error_map)
                     if map_dir:
                         luma_maps.append((s["pair"], got_maps[i][0].copy()))
+                if ssim_map:
+                    row["interpolated"]["ssim_map"] = _ssim_map_dict(got_smaps[i], ssim_map, got_maps[i] if error_map == ssim_map else None)
+                    if map_dir:
+                        luma_smaps.append((s["pair"], got_smaps[i][0].copy()))
                 rows.append(row)
             # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
             last = chunk[-1]["period"]
@@ -290,7 +373,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         aux.close()
         if filt is not None:
             filt.close()
-        for b in free_in + free_out + list(src.values()) + ([maps_buf] if maps_buf is not None else []):
+        for b in free_in + free_out + list(src.values()) + [b for b in (maps_buf, smaps_buf) if b is not None]:
             b.free()
     worst = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["psnr"] is None else r["interpolated"]["Y"]["psnr"])
     clip = {"interpolated": _aggregate(rows, "interpolated", peak), "repeat": _aggregate(rows, "repeat", peak),
@@ -309,6 +392,16 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         clip["worst_tile"] = {"pair": top["pair"], "plane": "Y", "x": t["x"], "y": t["y"], "sse": t["sse"]}
         if map_dir:
             _write_map_pgms(map_dir, luma_maps, error_map, H, W)
+    if ssim_map:
+        # the worst luma tile of the clip by the pairs' own order (cross-multiplied integers; the first of equals: the earlier pair)
+        low = None
+        for r in rows:
+            for t in r["interpolated"]["ssim_map"]["Y"]["worst"][:1]:
+                if low is None or t["sum_loss_q32"] * low[1]["count"] > low[1]["sum_loss_q32"] * t["count"]:
+                    low = (r["pair"], t)
+        clip["worst_tile_ssim"] = None if low is None else {"pair": low[0], "plane": "Y", "x": low[1]["x"], "y": low[1]["y"], "ssim": low[1]["ssim"]}
+        if map_dir:
+            _write_ssim_pgms(map_dir, luma_smaps)
     return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
             "settings": dict(st, black_level=float(black), white_level=float(white)),
             "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
@@ -381,8 +474,11 @@ def parse_args(argv=None):
                     help="also score every comparison with the windowed SSIM (8 x 8 windows at stride 4): mean and worst window per plane")
     ap.add_argument("--map", type=int, default=0, choices=(0, 16, 32, 64), metavar="TILE",
                     help="also locate the error: per-tile error maps of every interpolation, tiles of 16, 32 or 64 luma pixels")
+    ap.add_argument("--ssim-map", type=int, default=0, choices=(0, 16, 32, 64), metavar="TILE",
+                    help="also locate the structural loss: per-tile SSIM maps of every interpolation on the tile grid of --map; beside --map TILE of "
+                         "the same size each worst tile carries its squared error too")
     ap.add_argument("--map-dir", default=None, metavar="DIR",
-                    help="with --map: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
+                    help="with --map or --ssim-map: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
     ap.add_argument("--report", default=None, help="write the reports as JSON")
     a = ap.parse_args(argv)
     if a.pix_fmt is None:
@@ -391,8 +487,8 @@ def parse_args(argv=None):
         a.hdr = True
     elif a.hdr:
         ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
-    if a.map_dir and not a.map:
-        ap.error("--map-dir needs --map TILE")
+    if a.map_dir and not a.map and not a.ssim_map:
+        ap.error("--map-dir needs --map TILE or --ssim-map TILE")
     try:
         a.sweeps = parse_sweeps(a.sweep)
     except ValueError as e:
@@ -422,7 +518,7 @@ def main(argv=None, device=None):
         map_dir = a.map_dir and (os.path.join(a.map_dir, f"setting{k:02d}") if len(a.sweeps) > 1 else a.map_dir)
         rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
                        scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
-                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, **st)
+                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, ssim_map=a.ssim_map, **st)
         reports.append(rep)
         c = rep["clip"]
         knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
@@ -432,7 +528,9 @@ def main(argv=None, device=None):
                   f"  SSIM Y/U/V {_ss(c['interpolated']['Y']['ssim'])} {_ss(c['interpolated']['U']['ssim'])} {_ss(c['interpolated']['V']['ssim'])}  "
                   f"repeat Y {_ss(c['repeat']['Y']['ssim'])}  worst window {_ss(c['interpolated']['Y']['min_ssim'])}  "
                   f"worst pair {c['worst_pair_ssim']['pair']} ({_ss(c['worst_pair_ssim']['ssim_y'])})" if a.ssim else "") + (
-                  f"  worst tile pair {c['worst_tile']['pair']} at ({c['worst_tile']['x']}, {c['worst_tile']['y']}) sse {c['worst_tile']['sse']}" if a.map else ""))
+                  f"  worst tile pair {c['worst_tile']['pair']} at ({c['worst_tile']['x']}, {c['worst_tile']['y']}) sse {c['worst_tile']['sse']}" if a.map else "") + (
+                  f"  worst SSIM tile pair {c['worst_tile_ssim']['pair']} at ({c['worst_tile_ssim']['x']}, {c['worst_tile_ssim']['y']}) "
+                  f"{_ss(c['worst_tile_ssim']['ssim'])}" if a.ssim_map and c.get("worst_tile_ssim") else ""))
     if a.report:
         with open(a.report, "w") as f:
             json.dump({"input": a.input, "reports": reports}, f, indent=1)

@@ -462,6 +462,39 @@ int hf_frame_ssim_read(hf_ctx* ctx, int first_slot, int n, struct hf_frame_ssim*
 int hf_frame_ssim(hf_ctx* ctx, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar, int peak,
                   struct hf_frame_ssim* out);
 
+/* ---- Per-tile SSIM maps on the device: WHERE a frame is torn ----
+ * hf_frame_ssim's max_loss_q32 is the score of a plane's worst window, not its position, and the error maps above hold only squared
+ * and absolute error, which a ghost passes and a sharp, slightly misplaced edge fails.  This keeps the windowed SSIM per tile of the
+ * error maps' grid, so that the two maps join entry by entry.  Pairs, strides, layouts, planes, compared columns, the peak rule, the
+ * constants, the window terms and the window loss are those of hf_frame_ssim_enqueue, steps 1 to 5, unchanged; step by step:
+ *   1. Tiles.  `tile`, tw and th are those of hf_frame_error_map_shape: 16, 32 or 64 luma pixels (HF_ERROR_MAP_TILES_OK),
+ *      tw = (frame_width + tile - 1) / tile, th = (frame_height + tile - 1) / tile.  The tile edge in a plane's own elements is
+ *      te = tile for Y and tile / 2 for U and V (always a multiple of 4): tile (i, j) is the picture area of the error map's tile (i, j).
+ *   2. Which tile owns a window.  Window (i, j) of a plane covers elements 4 i .. 4 i + 7 by 4 j .. 4 j + 7 and belongs to the ONE tile
+ *      that holds its first element: tile (4 i / te, 4 j / te).  A window whose first block is the last block column or row of a tile
+ *      reaches 4 elements into the neighbouring tile and still belongs to the first.
+ *   3. Per tile and plane:  sum_loss_q32 = sum of the losses of its windows,  max_loss_q32 = the largest,  count = their number
+ *      (a 64 x 64 tile holds 256 windows of at most 2^33 each: sums stay below 2^42).  Mean SSIM of a tile = 1 - sum_loss_q32 / 2^32 /
+ *      count.
+ *   4. A tile may own no window: in the last column or row where fewer than 8 elements remain past the tile's first element, where the
+ *      unused w & 3 / h & 3 remainder cuts the last window, or in a plane without any window.  It is written as zeros, count = 0.
+ *   5. One map is `struct hf_ssim_tile [3][th][tw]`, plane 0 Y, 1 U, 2 V: bytes_per_map = 72 tw th.  device_maps is ONE caller-owned
+ *      device buffer of n bytes_per_map bytes, 16-byte aligned; the map of pair i starts at byte i bytes_per_map.
+ *   6. EVERY entry of every map is written by the launch, zeros included: the caller does not clear the buffer.  Per pair and plane the
+ *      sum of sum_loss_q32 over the tiles is hf_frame_ssim's sum_loss_q32, the largest max_loss_q32 its max_loss_q32, the sum of count
+ *      its count.  Equal frames give zero losses.
+ *   hf_frame_ssim_map_shape    tw, th and bytes_per_map of ctx's geometry for a tile (any of the three results may be NULL).
+ *   hf_frame_ssim_map_enqueue  only enqueues, ordered exactly like hf_frame_error_enqueue (behind every warp, copy and update of ctx,
+ *                              the warp stream of an HF_FLAG_DUAL_STREAM context included; a batch member on its batch's stream).
+ *                              Read the maps with hf_memcpy_d2h after hf_sync.  The frames must stay as they are until it has run.
+ *                              The SSIM slots and the error slots are untouched.
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued: everything hf_frame_ssim_enqueue refuses but the slot range (there are no slots), a
+ * tile outside {16, 32, 64}, a NULL or misaligned device_maps.  Additive to ABI version 6. */
+struct hf_ssim_tile { uint64_t sum_loss_q32; uint64_t max_loss_q32; uint32_t count; uint32_t reserved; };   /* 24 bytes, reserved = 0 */
+int hf_frame_ssim_map_shape(const hf_ctx* ctx, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map);
+int hf_frame_ssim_map_enqueue(hf_ctx* ctx, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b,
+                              int planar, int peak, int tile, void* device_maps);
+
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
 /* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
