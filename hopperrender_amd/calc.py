@@ -168,6 +168,15 @@ class OpticalFlowCalc:
         capi.check(self._lib.hf_download_frame_device(self._ctx, C.c_void_p(dev_ptr)), self._ctx)
 
     # ---- frame error sums on the device (hf_frame_error*) ----
+    def _pair_args(self, who, a_ptrs, b_ptrs, stride_a, stride_b, planar):
+        """(n, a table, b table, stride_a, stride_b, planar) as ctypes arguments of the four enqueue calls below; strides 0 = the frame width"""
+        n = len(a_ptrs)
+        if len(b_ptrs) != n:
+            raise ValueError(who + ": as many b frames as a frames")
+        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
+        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
+        return n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth, 1 if planar else 0
+
     @staticmethod
     def _frame_error_dict(e):
         """struct hf_frame_error as {'Y': {...}, 'U': {...}, 'V': {...}} of plain ints: sse, sad, max_abs, n_differ, count"""
@@ -176,13 +185,8 @@ class OpticalFlowCalc:
     def frameErrorEnqueue(self, a_ptrs, b_ptrs, first_slot=0, stride_a=0, stride_b=0, planar=False):
         """hf_frame_error_enqueue: compare device frames a_ptrs[i] and b_ptrs[i] into result slot first_slot + i, behind everything this
         context has enqueued; only enqueues.  Strides in elements, 0 = the frame width."""
-        n = len(a_ptrs)
-        if len(b_ptrs) != n:
-            raise ValueError("frameErrorEnqueue: as many b frames as a frames")
-        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
-        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
-        capi.check(self._lib.hf_frame_error_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
-                                                    1 if planar else 0, int(first_slot)), self._ctx)
+        args = self._pair_args("frameErrorEnqueue", a_ptrs, b_ptrs, stride_a, stride_b, planar)
+        capi.check(self._lib.hf_frame_error_enqueue(self._ctx, *args, int(first_slot)), self._ctx)
 
     def frameErrorRead(self, first_slot, n):
         """hf_frame_error_read: wait for this context's work and return result slots [first_slot, first_slot + n) as dicts."""
@@ -208,13 +212,8 @@ class OpticalFlowCalc:
         """hf_frame_error_map_enqueue: the per-tile error sums of device frames a_ptrs[i] against b_ptrs[i] into map i of the device buffer
         at maps_ptr (len(a_ptrs) maps of frameErrorMapShape(tile)[2] bytes, 16-byte aligned), behind everything this context has
         enqueued; only enqueues.  Download the buffer after sync() and view it with frame_error_maps()."""
-        n = len(a_ptrs)
-        if len(b_ptrs) != n:
-            raise ValueError("frameErrorMapEnqueue: as many b frames as a frames")
-        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
-        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
-        capi.check(self._lib.hf_frame_error_map_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
-                                                        1 if planar else 0, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
+        args = self._pair_args("frameErrorMapEnqueue", a_ptrs, b_ptrs, stride_a, stride_b, planar)
+        capi.check(self._lib.hf_frame_error_map_enqueue(self._ctx, *args, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
 
     # ---- windowed SSIM on the device (hf_frame_ssim*) ----
     @staticmethod
@@ -231,13 +230,8 @@ class OpticalFlowCalc:
     def frameSsimEnqueue(self, a_ptrs, b_ptrs, first_slot=0, stride_a=0, stride_b=0, planar=False, peak=0):
         """hf_frame_ssim_enqueue: score device frames a_ptrs[i] against b_ptrs[i] into SSIM slot first_slot + i, behind everything this
         context has enqueued; only enqueues.  Strides in elements, 0 = the frame width; peak 0 = the format's own."""
-        n = len(a_ptrs)
-        if len(b_ptrs) != n:
-            raise ValueError("frameSsimEnqueue: as many b frames as a frames")
-        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
-        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
-        capi.check(self._lib.hf_frame_ssim_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
-                                                   1 if planar else 0, int(peak), int(first_slot)), self._ctx)
+        args = self._pair_args("frameSsimEnqueue", a_ptrs, b_ptrs, stride_a, stride_b, planar)
+        capi.check(self._lib.hf_frame_ssim_enqueue(self._ctx, *args, int(peak), int(first_slot)), self._ctx)
 
     def frameSsimRead(self, first_slot, n):
         """hf_frame_ssim_read: wait for this context's work and return SSIM slots [first_slot, first_slot + n) as dicts."""
@@ -264,13 +258,8 @@ class OpticalFlowCalc:
         """hf_frame_ssim_map_enqueue: the windowed SSIM of device frames a_ptrs[i] against b_ptrs[i] per tile into map i of the device
         buffer at maps_ptr (len(a_ptrs) maps of frameSsimMapShape(tile)[2] bytes, 16-byte aligned), behind everything this context has
         enqueued; only enqueues.  Download the buffer after sync() and view it with frame_ssim_maps()."""
-        n = len(a_ptrs)
-        if len(b_ptrs) != n:
-            raise ValueError("frameSsimMapEnqueue: as many b frames as a frames")
-        a = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in a_ptrs])
-        b = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in b_ptrs])
-        capi.check(self._lib.hf_frame_ssim_map_enqueue(self._ctx, n, a, b, int(stride_a) or self.m_frameWidth, int(stride_b) or self.m_frameWidth,
-                                                       1 if planar else 0, int(peak), int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
+        args = self._pair_args("frameSsimMapEnqueue", a_ptrs, b_ptrs, stride_a, stride_b, planar)
+        capi.check(self._lib.hf_frame_ssim_map_enqueue(self._ctx, *args, int(peak), int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
 
     def setOutputBuffer(self, dev_ptr):
         capi.check(self._lib.hf_set_output_buffer(self._ctx, C.c_void_p(dev_ptr or 0)), self._ctx)

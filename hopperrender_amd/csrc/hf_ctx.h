@@ -11,7 +11,9 @@
 //                    fused or member-by-member warps, predicated copy, planar conversion): hf_interpolate_period is its n = 1 case
 //   hf_batch.hip     hf_batch: the same calls for up to 32 contexts of one geometry as one set of launches (throughput drivers), and whole
 //                    clips through a batch with the warp-or-copy decision taken on the device (hf_batch_run_period_auto, hf_scene.hip)
-//   hf_metrics.hip   frame error sums on the device (hf_frame_error*): kernel, launcher and the three calls
+//   hf_metrics.hip   the four frame metrics on the device -- error sums, windowed SSIM, per-tile error maps, per-tile SSIM maps (hf_frame_error*,
+//                    hf_frame_ssim*, hf_frame_error_map*, hf_frame_ssim_map*): their kernels, ONE frame layout and launcher tail on the host,
+//                    ONE slot enqueue / read and ONE map shape / enqueue behind the ten calls
 //   hf_async_io.hip  pinned asynchronous H2D / D2H on side streams (hf_update_frame_async: the H2D, then update_frames;
 //                    hf_download_frame_async, hf_wait_*)
 //

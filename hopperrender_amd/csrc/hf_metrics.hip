@@ -18,10 +18,13 @@
 // workgroup's waves (LDS), and ONE atomicAdd / atomicMax per quantity, plane and workgroup into the pair's slot, which a hipMemsetAsync
 // ahead of the launch zeroed.  Grid-stride over at most ~2048 workgroups per launch, one at least per pair.
 //
-// Further down: the windowed SSIM of the same pairs (hf_frame_ssim*), with its own kernel, launcher and slots; and the per-tile error
-// maps (hf_frame_error_map*): the same sums per tile of 16, 32 or 64 luma pixels; a workgroup reads a band of tile rows in memory
-// order, a tile's lanes are reduced by shuffles (and waves that shared its rows through LDS), every entry is stored once -- no atomics,
-// no memset.  The lane mapping is described there.
+// Further down: the windowed SSIM of the same pairs (hf_frame_ssim*), with its own kernel and slots; the per-tile error maps
+// (hf_frame_error_map*): the same sums per tile of 16, 32 or 64 luma pixels, every entry stored once -- no atomics, no memset; and the
+// per-tile SSIM maps (hf_frame_ssim_map*), which run the SSIM kernel's block step (ssim_fetch, ssim_sums, ssim_unit_windows: written
+// once, over a lane's positions SsimPos) on patches cut to the tile grid.  Then the host side, written once for the four launches:
+// frame_layout() (how a frame lies in memory and whether the launch may load 16 bytes at a time), the pointer tables, ssim_plane(),
+// the kernel of a format and resident_workgroups(); and the C calls: one enqueue and one read for both families of slots, one shape and
+// one enqueue for both kinds of maps.
 #include <type_traits>
 
 #include "hf_ctx.h"
@@ -198,8 +201,6 @@ __global__ void __launch_bounds__(kErrBlock) frame_error_kernel(const ErrorArgs 
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // ---- Windowed SSIM (hf_frame_ssim*; the definition is in include/hopperflow.h) ----
 // Per plane: integer sums s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b over the 4 x 4 blocks of the plane; a window is
 // 2 x 2 blocks; its score goes through five double operations and comes back as the integer loss 2^32 - round(ssim 2^32).  The same
@@ -349,9 +350,15 @@ __device__ __forceinline__ void ssim_add_row(SsimWide<T>* w, const uint4& a, con
     }
 }
 
-// where tile t of a frame lies: plane (0 luma; 1 interleaved UV or U; 2 V) and position
+// where a tile (or a patch of the map kernel below) starts: plane (0 luma; 1 interleaved UV or U; 2 V), first unit, first block row
+struct SsimAt {
+    uint32_t pl, u0, j0;
+};
+// where tile t of a frame lies.  at() is formed at every use: as products carried through the tile loop, u0 and j0 cost the 8-bit
+// kernels 4 .. 7 % more instructions
 struct SsimTileAt {
     uint32_t pl, tx, ty;
+    __device__ __forceinline__ SsimAt at() const { return SsimAt{pl, tx * (uint32_t)(kSsimUnitsX - 1), ty * (uint32_t)(kSsimRows - 1)}; }
 };
 template <bool PLANAR>
 __device__ __forceinline__ SsimTileAt ssim_locate(const SsimShape& s, uint32_t t) {
@@ -360,8 +367,23 @@ __device__ __forceinline__ SsimTileAt ssim_locate(const SsimShape& s, uint32_t t
     return SsimTileAt{pl, l - ty * s.pl[pl].tiles_x, ty};
 }
 
-// a lane's two (unit, block row) positions of a tile
+// a lane's two positions (unit, block row) within its tile or patch; lr = kSsimNoRow: no such position
 constexpr int kSsimPerLane = kSsimItems / kSsimBlock;
+constexpr uint32_t kSsimNoRow = ~0u;
+struct SsimPos {
+    uint32_t lu[kSsimPerLane], lr[kSsimPerLane];
+    __device__ __forceinline__ bool none(uint32_t n) const { return lr[n] == kSsimNoRow; }
+};
+// ... of a tile: its shape is a compile-time constant, so every use folds into shifts and masks of threadIdx.x and none() into false
+__device__ __forceinline__ SsimPos ssim_tile_pos() {
+    SsimPos ps;
+#pragma unroll
+    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
+        const uint32_t it = threadIdx.x + n * kSsimBlock;
+        ps.lu[n] = it % kSsimUnitsX; ps.lr[n] = it / kSsimUnitsX;
+    }
+    return ps;
+}
 struct SsimRows {        // the 16-byte loads of a tile still in flight: [position][row] of either side
     uint4 a[kSsimPerLane][4], b[kSsimPerLane][4];
 };
@@ -371,36 +393,36 @@ __device__ __forceinline__ bool ssim_wide(const SsimPlane& p, uint32_t u, uint32
     return p.vec && j < p.bh && u * EL + EL <= p.w_row;
 }
 
-// step 0 of a tile: issue its wide loads.  Called for the NEXT tile ahead of the windows of the current one, which hide their latency.
-template <typename T>
-__device__ __forceinline__ void ssim_fetch(const T* __restrict__ fa, const T* __restrict__ fb, const SsimShape& s, const SsimPlane& p,
-                                           const SsimTileAt& at, SsimRows& rows) {
+// The block step of the SSIM kernel and of the map kernel below, over the positions ps of the tile or patch at `at`.  SITE: the first of
+// two debug-bounds site ids (elems_a / elems_b: the extent of a frame of either side); LW: units of a row of blocks in LDS.
+// step 0: issue the wide loads.  Called for the NEXT tile ahead of the windows of the current one, which hide their latency.
+template <typename T, int SITE>
+__device__ __forceinline__ void ssim_fetch(const T* __restrict__ fa, const T* __restrict__ fb, size_t elems_a, size_t elems_b, const SsimPlane& p,
+                                           const SsimAt& at, const SsimPos& ps, SsimRows& rows) {
     constexpr uint32_t EL = 16 / sizeof(T);
-    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
 #pragma unroll
     for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t it = threadIdx.x + n * kSsimBlock, u = u0 + it % kSsimUnitsX, j = j0 + it / kSsimUnitsX;
-        if (!ssim_wide<T>(p, u, j)) continue;
+        const uint32_t u = at.u0 + ps.lu[n], j = at.j0 + ps.lr[n];
+        if (ps.none(n) || !ssim_wide<T>(p, u, j)) continue;
 #pragma unroll
         for (uint32_t r = 0; r < 4; r++) {
             const size_t ia = p.base_a + (size_t)(4u * j + r) * p.pitch_a + u * EL, ib = p.base_b + (size_t)(4u * j + r) * p.pitch_b + u * EL;
-            HF_DBG_CHECK(ia + EL <= s.elems_a && ib + EL <= s.elems_b, 255);
+            HF_DBG_CHECK(ia + EL <= elems_a && ib + EL <= elems_b && u * EL + EL <= p.w_row, SITE + 0);
             rows.a[n][r] = *reinterpret_cast<const uint4*>(fa + ia); rows.b[n][r] = *reinterpret_cast<const uint4*>(fb + ib);
         }
     }
 }
 
-// step 1: the block sums of the tile into LDS, from the rows fetched or -- unaligned frames, the ragged end of a row -- element by
-// element.  CH = 2: an interleaved UV plane.
-template <typename T, int CH>
-__device__ __forceinline__ void ssim_sums(const T* __restrict__ fa, const T* __restrict__ fb, const SsimShape& s, const SsimPlane& p,
-                                          const SsimTileAt& at, const SsimRows& rows, SsimBlk<T> (*lds)[4 / sizeof(T)][kSsimUnitsX]) {
+// step 1: the block sums into LDS, from the rows fetched or -- unaligned frames, the ragged end of a row -- element by element.
+// CH = 2: an interleaved UV plane.
+template <typename T, int CH, int LW, int SITE>
+__device__ __forceinline__ void ssim_sums(const T* __restrict__ fa, const T* __restrict__ fb, size_t elems_a, size_t elems_b, const SsimPlane& p,
+                                          const SsimAt& at, const SsimPos& ps, const SsimRows& rows, SsimBlk<T> (*lds)[4 / sizeof(T)][LW]) {
     constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
-    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
 #pragma unroll
     for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t it = threadIdx.x + n * kSsimBlock, lu = it % kSsimUnitsX, lr = it / kSsimUnitsX, u = u0 + lu, j = j0 + lr;
-        if (j >= p.bh || u * BPU >= p.bw) continue;
+        const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
+        if (ps.none(n) || j >= p.bh || u * BPU >= p.bw) continue;
         SsimBlk<T> blk[NB] = {};
         if (ssim_wide<T>(p, u, j)) {
             SsimWide<T> w[NB];
@@ -420,7 +442,7 @@ __device__ __forceinline__ void ssim_sums(const T* __restrict__ fa, const T* __r
                         for (uint32_t e = 0; e < 4; e++) {
                             const uint32_t x = (4u * i + e) * CH + c;
                             const size_t ia = oa + (size_t)r * p.pitch_a + x, ib = ob + (size_t)r * p.pitch_b + x;
-                            HF_DBG_CHECK(x < p.w_row && ia < s.elems_a && ib < s.elems_b, 256);
+                            HF_DBG_CHECK(x < p.w_row && ia < elems_a && ib < elems_b, SITE + 1);
                             blk[c * BPU + k].add1(fa[ia], fb[ib]);
                         }
                 }
@@ -430,30 +452,39 @@ __device__ __forceinline__ void ssim_sums(const T* __restrict__ fa, const T* __r
     }
 }
 
-// step 2, behind a barrier: the windows of the tile; channel 0 into acc0 and channel 1 into acc1 (CH = 1: acc0 alone)
-template <typename T, int CH>
-__device__ __forceinline__ void ssim_windows(const SsimShape& s, const SsimPlane& p, const SsimTileAt& at,
-                                             const SsimBlk<T> (*lds)[4 / sizeof(T)][kSsimUnitsX], SsimLane& acc0, SsimLane& acc1) {
+// step 2, behind a barrier, for one position that owns windows: the column sums of unit u (at lu, lr in LDS) and of the first block to
+// its right over this block row and the next, and each window of the unit as each(loss, channel, block within the unit)
+template <typename T, int CH, int LW, typename F>
+__device__ __forceinline__ void ssim_unit_windows(const SsimPlane& p, uint32_t u, uint32_t lu, uint32_t lr, long long c1, long long c2,
+                                                  const SsimBlk<T> (*lds)[4 / sizeof(T)][LW], F&& each) {
     constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
-    const uint32_t u0 = at.tx * (kSsimUnitsX - 1), j0 = at.ty * (kSsimRows - 1);
+#pragma unroll
+    for (uint32_t c = 0; c < (uint32_t)CH; c++) {
+        SsimBlk<T> col[BPU + 1];   // blocks (i, j) + (i, j + 1) of the unit's blocks and of the first one to the right
+#pragma unroll
+        for (uint32_t k = 0; k < BPU; k++) col[k] = lds[lr][c * BPU + k][lu] + lds[lr + 1][c * BPU + k][lu];
+        col[BPU] = lds[lr][c * BPU][lu + 1] + lds[lr + 1][c * BPU][lu + 1];   // (never written where no block is: then no window uses it)
+#pragma unroll
+        for (uint32_t k = 0; k < BPU; k++) {
+            if (u * BPU + k + 1 >= p.bw) continue;
+            each(ssim_loss<T>(col[k] + col[k + 1], c1, c2), c, k);
+        }
+    }
+}
+
+// ... of a tile; channel 0 into acc0 and channel 1 into acc1 (CH = 1: acc0 alone)
+template <typename T, int CH>
+__device__ __forceinline__ void ssim_windows(const SsimShape& s, const SsimPlane& p, const SsimAt& at, const SsimPos& ps,
+                                             const SsimBlk<T> (*lds)[4 / sizeof(T)][kSsimUnitsX], SsimLane& acc0, SsimLane& acc1) {
+    constexpr uint32_t BPU = 4 / sizeof(T) / CH;
 #pragma unroll
     for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t it = threadIdx.x + n * kSsimBlock, lu = it % kSsimUnitsX, lr = it / kSsimUnitsX, u = u0 + lu, j = j0 + lr;
+        const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
         if (lu + 1 >= (uint32_t)kSsimUnitsX || lr + 1 >= (uint32_t)kSsimRows || j + 1 >= p.bh || u * BPU + 1 >= p.bw) continue;
-#pragma unroll
-        for (uint32_t c = 0; c < (uint32_t)CH; c++) {
-            SsimBlk<T> col[BPU + 1];   // blocks (i, j) + (i, j + 1) of the unit's blocks and of the first one to the right
-#pragma unroll
-            for (uint32_t k = 0; k < BPU; k++) col[k] = lds[lr][c * BPU + k][lu] + lds[lr + 1][c * BPU + k][lu];
-            col[BPU] = lds[lr][c * BPU][lu + 1] + lds[lr + 1][c * BPU][lu + 1];   // (never written where no block is: then no window uses it)
+        ssim_unit_windows<T, CH, kSsimUnitsX>(p, u, lu, lr, s.c1, s.c2, lds, [&](double loss, uint32_t c, uint32_t) {
             SsimLane& acc = c ? acc1 : acc0;
-#pragma unroll
-            for (uint32_t k = 0; k < BPU; k++) {
-                if (u * BPU + k + 1 >= p.bw) continue;
-                const double loss = ssim_loss<T>(col[k] + col[k + 1], s.c1, s.c2);
-                acc.sum += loss; acc.mx = fmax(acc.mx, loss); acc.cnt++;
-            }
-        }
+            acc.sum += loss; acc.mx = fmax(acc.mx, loss); acc.cnt++;
+        });
     }
 }
 
@@ -469,19 +500,20 @@ __global__ void __launch_bounds__(kSsimBlock) frame_ssim_kernel(const SsimArgs a
     SsimRows rows = {};
     uint32_t t = blockIdx.x;
     SsimTileAt at = {0, 0, 0};
-    if (t < s.tiles) { at = ssim_locate<PLANAR>(s, t); ssim_fetch<T>(fa, fb, s, s.pl[at.pl], at, rows); }
+    const SsimPos ps = ssim_tile_pos();
+    if (t < s.tiles) { at = ssim_locate<PLANAR>(s, t); ssim_fetch<T, 255>(fa, fb, s.elems_a, s.elems_b, s.pl[at.pl], at.at(), ps, rows); }
     while (t < s.tiles) {
-        if (at.pl == 0)   ssim_sums<T, 1>(fa, fb, s, s.pl[0], at, rows, lds);
-        else if (!PLANAR) ssim_sums<T, 2>(fa, fb, s, s.pl[1], at, rows, lds);
-        else              ssim_sums<T, 1>(fa, fb, s, s.pl[at.pl], at, rows, lds);
+        if (at.pl == 0)   ssim_sums<T, 1, kSsimUnitsX, 255>(fa, fb, s.elems_a, s.elems_b, s.pl[0], at.at(), ps, rows, lds);
+        else if (!PLANAR) ssim_sums<T, 2, kSsimUnitsX, 255>(fa, fb, s.elems_a, s.elems_b, s.pl[1], at.at(), ps, rows, lds);
+        else              ssim_sums<T, 1, kSsimUnitsX, 255>(fa, fb, s.elems_a, s.elems_b, s.pl[at.pl], at.at(), ps, rows, lds);
         __syncthreads();
         const uint32_t tn = t + gridDim.x;
         SsimTileAt nx = at;
-        if (tn < s.tiles) { nx = ssim_locate<PLANAR>(s, tn); ssim_fetch<T>(fa, fb, s, s.pl[nx.pl], nx, rows); }
-        if (at.pl == 0)       ssim_windows<T, 1>(s, s.pl[0], at, lds, acc[0], acc[0]);
-        else if (!PLANAR)     ssim_windows<T, 2>(s, s.pl[1], at, lds, acc[1], acc[2]);
-        else if (at.pl == 1)  ssim_windows<T, 1>(s, s.pl[1], at, lds, acc[1], acc[1]);
-        else                  ssim_windows<T, 1>(s, s.pl[2], at, lds, acc[2], acc[2]);
+        if (tn < s.tiles) { nx = ssim_locate<PLANAR>(s, tn); ssim_fetch<T, 255>(fa, fb, s.elems_a, s.elems_b, s.pl[nx.pl], nx.at(), ps, rows); }
+        if (at.pl == 0)       ssim_windows<T, 1>(s, s.pl[0], at.at(), ps, lds, acc[0], acc[0]);
+        else if (!PLANAR)     ssim_windows<T, 2>(s, s.pl[1], at.at(), ps, lds, acc[1], acc[2]);
+        else if (at.pl == 1)  ssim_windows<T, 1>(s, s.pl[1], at.at(), ps, lds, acc[1], acc[1]);
+        else                  ssim_windows<T, 1>(s, s.pl[2], at.at(), ps, lds, acc[2], acc[2]);
         __syncthreads();   // the next tile overwrites the blocks
         t = tn; at = nx;
     }
@@ -705,8 +737,8 @@ __global__ void __launch_bounds__(kMapBlock) frame_error_map_kernel(const MapArg
 // ---- Per-tile SSIM maps (hf_frame_ssim_map*; the definition is in include/hopperflow.h) ----
 // The windowed SSIM above kept per tile of the error maps' grid: one hf_ssim_tile {sum_loss_q32, max_loss_q32, count} per tile and plane,
 // in one caller-owned buffer for all pairs of the launch.  A window belongs to the tile that holds its first block.  Same pointer table,
-// layouts, pitches, unit (16 bytes of four rows on each side), block sums and window loss as the SSIM kernel, whose SsimPlane, SsimBlk,
-// SsimWide, ssim_add_row, ssim_wide, SsimRows and ssim_loss it uses as they are.
+// layouts, pitches, unit (16 bytes of four rows on each side) and block step as the SSIM kernel: ssim_fetch, ssim_sums and
+// ssim_unit_windows run here over the positions of a patch (smap_pos) and an LDS row of kSmapWidth units.
 //
 // The mapping.  A PATCH is what a workgroup takes at a time: kSmapRows = 16 block rows of windows by pu units of windows, and one block
 // row and one unit of halo behind them (read again by the neighbouring patch: 17 / 16 x (pu + 1) / pu = 1.10 of the frame, as in the
@@ -760,24 +792,19 @@ struct SmapArgs {
 };
 static_assert(sizeof(SmapArgs) <= 4096, "kernel arguments: 4 KB");
 
-struct SmapAt {          // where a patch lies: plane, first unit, first block row
-    uint32_t pl, u0, j0;
-};
 template <bool PLANAR>
-__device__ __forceinline__ SmapAt smap_locate(const SmapArgs& a, uint32_t t) {
+__device__ __forceinline__ SsimAt smap_locate(const SmapArgs& a, uint32_t t) {   // where patch t of a frame lies
     const uint32_t pl = t < a.pl[1].p.tile_first ? 0u : (!PLANAR || t < a.pl[2].p.tile_first) ? 1u : 2u;
     const uint32_t l = t - a.pl[pl].p.tile_first, py = l / a.pl[pl].p.tiles_x;
-    return SmapAt{pl, (l - py * a.pl[pl].p.tiles_x) * a.pl[pl].pu, py * (uint32_t)kSmapRows};
+    return SsimAt{pl, (l - py * a.pl[pl].p.tiles_x) * a.pl[pl].pu, py * (uint32_t)kSmapRows};
 }
-struct SmapPos {         // a lane's two positions (unit, block row) within a patch pw units wide; lr > kSmapRows: none
-    uint32_t lu[kSsimPerLane], lr[kSsimPerLane];
-};
-__device__ __forceinline__ SmapPos smap_pos(uint32_t pw) {
-    SmapPos ps;
+// a lane's two positions within a patch pw units wide (halo included) and kSmapRows + 1 block rows high
+__device__ __forceinline__ SsimPos smap_pos(uint32_t pw) {
+    SsimPos ps;
 #pragma unroll
     for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t it = threadIdx.x + n * kSmapBlock;
-        ps.lr[n] = it / pw; ps.lu[n] = it - ps.lr[n] * pw;
+        const uint32_t it = threadIdx.x + n * kSmapBlock, lr = it / pw;
+        ps.lr[n] = lr > (uint32_t)kSmapRows ? kSsimNoRow : lr; ps.lu[n] = it - lr * pw;
     }
     return ps;
 }
@@ -785,90 +812,23 @@ struct SmapPart {        // the windows of one position in one tile: summed and 
     double sum, mx;
 };
 
-// step 0 of a patch: issue its wide loads
-template <typename T>
-__device__ __forceinline__ void smap_fetch(const T* __restrict__ fa, const T* __restrict__ fb, const SmapArgs& a, const SsimPlane& p,
-                                           const SmapAt& at, const SmapPos& ps, SsimRows& rows) {
-    constexpr uint32_t EL = 16 / sizeof(T);
-#pragma unroll
-    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t u = at.u0 + ps.lu[n], j = at.j0 + ps.lr[n];
-        if (ps.lr[n] > (uint32_t)kSmapRows || !ssim_wide<T>(p, u, j)) continue;
-#pragma unroll
-        for (uint32_t r = 0; r < 4; r++) {
-            const size_t ia = p.base_a + (size_t)(4u * j + r) * p.pitch_a + u * EL, ib = p.base_b + (size_t)(4u * j + r) * p.pitch_b + u * EL;
-            HF_DBG_CHECK(ia + EL <= a.elems_a && ib + EL <= a.elems_b && u * EL + EL <= p.w_row, 271);
-            rows.a[n][r] = *reinterpret_cast<const uint4*>(fa + ia); rows.b[n][r] = *reinterpret_cast<const uint4*>(fb + ib);
-        }
-    }
-}
-
-// step 1: the block sums of the patch into LDS (ssim_sums with the patch's geometry)
-template <typename T, int CH>
-__device__ __forceinline__ void smap_sums(const T* __restrict__ fa, const T* __restrict__ fb, const SmapArgs& a, const SsimPlane& p,
-                                          const SmapAt& at, const SmapPos& ps, const SsimRows& rows, SsimBlk<T> (*lds)[4 / sizeof(T)][kSmapWidth]) {
-    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
-#pragma unroll
-    for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
-        const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
-        if (lr > (uint32_t)kSmapRows || j >= p.bh || u * BPU >= p.bw) continue;
-        SsimBlk<T> blk[NB] = {};
-        if (ssim_wide<T>(p, u, j)) {
-            SsimWide<T> w[NB];
-#pragma unroll
-            for (uint32_t r = 0; r < 4; r++) ssim_add_row<T, CH>(w, rows.a[n][r], rows.b[n][r]);
-#pragma unroll
-            for (uint32_t k = 0; k < NB; k++) blk[k] = w[k].finish();
-        } else {
-            const size_t oa = p.base_a + (size_t)(4u * j) * p.pitch_a, ob = p.base_b + (size_t)(4u * j) * p.pitch_b;
-#pragma unroll
-            for (uint32_t c = 0; c < (uint32_t)CH; c++)
-#pragma unroll
-                for (uint32_t k = 0; k < BPU; k++) {
-                    const uint32_t i = u * BPU + k;
-                    if (i >= p.bw) continue;   // (a unit past the last whole block of the row: nothing of it is read)
-                    for (uint32_t r = 0; r < 4; r++)
-                        for (uint32_t e = 0; e < 4; e++) {
-                            const uint32_t x = (4u * i + e) * CH + c;
-                            const size_t ia = oa + (size_t)r * p.pitch_a + x, ib = ob + (size_t)r * p.pitch_b + x;
-                            HF_DBG_CHECK(x < p.w_row && ia < a.elems_a && ib < a.elems_b, 272);
-                            blk[c * BPU + k].add1(fa[ia], fb[ib]);
-                        }
-                }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < NB; k++) lds[lr][k][lu] = blk[k];
-    }
-}
-
 // step 2, behind a barrier: the windows of every position that owns some, per position into part[block row][value][unit]
 template <typename T, int CH>
-__device__ __forceinline__ void smap_windows(const SmapArgs& a, const SmapPlane& m, const SmapAt& at, const SmapPos& ps,
+__device__ __forceinline__ void smap_windows(const SmapArgs& a, const SmapPlane& m, const SsimAt& at, const SsimPos& ps,
                                              const SsimBlk<T> (*lds)[4 / sizeof(T)][kSmapWidth], SmapPart (*part)[2][32]) {
-    constexpr uint32_t NB = 4 / sizeof(T), BPU = NB / CH;
+    constexpr uint32_t BPU = 4 / sizeof(T) / CH;
     const SsimPlane& p = m.p;
 #pragma unroll
     for (uint32_t n = 0; n < (uint32_t)kSsimPerLane; n++) {
         const uint32_t lu = ps.lu[n], lr = ps.lr[n], u = at.u0 + lu, j = at.j0 + lr;
-        if (lu >= m.pu || lr >= (uint32_t)kSmapRows) continue;   // halo: its windows are the next patch's
+        if (lu >= m.pu || lr >= (uint32_t)kSmapRows) continue;   // halo (or no position): its windows are the next patch's
         SmapPart v[2] = {{0.0, 0.0}, {0.0, 0.0}};
-        if (j + 1 < p.bh && u * BPU + 1 < p.bw) {
-#pragma unroll
-            for (uint32_t c = 0; c < (uint32_t)CH; c++) {
-                SsimBlk<T> col[BPU + 1];   // blocks (i, j) + (i, j + 1) of the unit's blocks and of the first one to the right
-#pragma unroll
-                for (uint32_t k = 0; k < BPU; k++) col[k] = lds[lr][c * BPU + k][lu] + lds[lr + 1][c * BPU + k][lu];
-                col[BPU] = lds[lr][c * BPU][lu + 1] + lds[lr + 1][c * BPU][lu + 1];   // (never written where no block is: then no window uses it)
-#pragma unroll
-                for (uint32_t k = 0; k < BPU; k++) {
-                    if (u * BPU + k + 1 >= p.bw) continue;
-                    const double loss = ssim_loss<T>(col[k] + col[k + 1], a.c1, a.c2);
-                    const bool second = CH == 2 ? c == 1u : (BPU == 4 && k >= 2u && m.halves);
-                    SmapPart& t = v[second ? 1 : 0];
-                    t.sum += loss; t.mx = fmax(t.mx, loss);
-                }
-            }
-        }
+        if (j + 1 < p.bh && u * BPU + 1 < p.bw)
+            ssim_unit_windows<T, CH, kSmapWidth>(p, u, lu, lr, a.c1, a.c2, lds, [&](double loss, uint32_t c, uint32_t k) {
+                const bool second = CH == 2 ? c == 1u : (BPU == 4 && k >= 2u && m.halves);
+                SmapPart& t = v[second ? 1 : 0];
+                t.sum += loss; t.mx = fmax(t.mx, loss);
+            });
         part[lr][0][lu] = v[0]; part[lr][1][lu] = v[1];
     }
 }
@@ -889,7 +849,7 @@ __device__ __forceinline__ void smap_column(const SmapPart* col, double& sum, do
 
 // step 3, behind a second barrier: the tiles of the patch out of part[][][] into the pair's map
 template <int CH>
-__device__ __forceinline__ void smap_store(const SmapArgs& a, const SmapPlane& m, const SmapAt& at, unsigned f, const SmapPart (*part)[2][32]) {
+__device__ __forceinline__ void smap_store(const SmapArgs& a, const SmapPlane& m, const SsimAt& at, unsigned f, const SmapPart (*part)[2][32]) {
     const uint32_t lu = threadIdx.x & 31u, g = threadIdx.x >> 5;
     const uint32_t two = (CH == 2 || m.halves) ? 1u : 0u;                       // two values per position
     const uint32_t combos = ((uint32_t)kSmapRows >> m.lg_tb) << two;                // (value, tile row of the patch)
@@ -933,22 +893,25 @@ __global__ void __launch_bounds__(kSmapBlock) frame_ssim_map_kernel(const SmapAr
     const T* __restrict__ fb = static_cast<const T*>(a.b[f]);
     SsimRows rows = {};
     uint32_t t = blockIdx.x;
-    SmapAt at = {0, 0, 0};
-    SmapPos ps = {};
-    if (t < a.patches) { at = smap_locate<PLANAR>(a, t); ps = smap_pos(a.pl[at.pl].pu + 1u); smap_fetch<T>(fa, fb, a, a.pl[at.pl].p, at, ps, rows); }
+    SsimAt at = {0, 0, 0};
+    SsimPos ps = {};
+    if (t < a.patches) {
+        at = smap_locate<PLANAR>(a, t); ps = smap_pos(a.pl[at.pl].pu + 1u);
+        ssim_fetch<T, 271>(fa, fb, a.elems_a, a.elems_b, a.pl[at.pl].p, at, ps, rows);
+    }
     while (t < a.patches) {
         const SmapPlane& m = a.pl[at.pl];
         const bool uv = !PLANAR && at.pl != 0;   // an interleaved UV plane: two channels
-        if (uv) smap_sums<T, 2>(fa, fb, a, m.p, at, ps, rows, lds);
-        else    smap_sums<T, 1>(fa, fb, a, m.p, at, ps, rows, lds);
+        if (uv) ssim_sums<T, 2, kSmapWidth, 271>(fa, fb, a.elems_a, a.elems_b, m.p, at, ps, rows, lds);
+        else    ssim_sums<T, 1, kSmapWidth, 271>(fa, fb, a.elems_a, a.elems_b, m.p, at, ps, rows, lds);
         __syncthreads();
         const uint32_t tn = t + gridDim.x;
-        SmapAt nx = at;
-        SmapPos pn = ps;
+        SsimAt nx = at;
+        SsimPos pn = ps;
         if (tn < a.patches) {
             nx = smap_locate<PLANAR>(a, tn);
             if (a.pl[nx.pl].pu != m.pu) pn = smap_pos(a.pl[nx.pl].pu + 1u);
-            smap_fetch<T>(fa, fb, a, a.pl[nx.pl].p, nx, pn, rows);
+            ssim_fetch<T, 271>(fa, fb, a.elems_a, a.elems_b, a.pl[nx.pl].p, nx, pn, rows);
         }
         if (uv) smap_windows<T, 2>(a, m, at, ps, lds, part);
         else    smap_windows<T, 1>(a, m, at, ps, lds, part);
@@ -959,37 +922,100 @@ __global__ void __launch_bounds__(kSmapBlock) frame_ssim_map_kernel(const SmapAr
     }
 }
 
-// what every pair of a launch shares and the pointer tables, into the arguments of the error kernel or of the map kernel; false: n out
-// of range, or a frame beyond 2^32 work items
+// ---- The host side of the four launches ----
+// How a frame lies in memory (the layouts at the top of this file), derived HERE for all four launchers, and the one decision it takes:
+// wide loads need the row pitches of both sides AND the base of every frame of the launch 16-byte aligned (the chroma bases are whole
+// numbers of rows behind the frame's), so one unaligned frame turns them off for the whole launch.  ok = false: n outside 1 .. kMaxErrorPairs.
+struct FrameLayout {
+    bool ok, planar;
+    uint32_t H, W;
+    uint32_t bpp;                    // bytes per element
+    uint32_t pitch_ya, pitch_yb;     // row pitches of side a / b, elements
+    uint32_t pitch_ca, pitch_cb;
+    size_t base_ca, base_cb;         // first chroma row, elements
+    uint32_t rows_c;                 // chroma rows (planar: U's, then V's)
+    size_t elems_a, elems_b;         // extent of a frame of side a / b (debug-bounds)
+    int vec_y, vec_c;                // every luma / chroma row of every frame of the launch starts 16-byte aligned
+};
+FrameLayout frame_layout(int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b) {
+    FrameLayout l{};
+    if (n < 1 || n > kMaxErrorPairs) return l;
+    l.ok = true; l.planar = planar; l.H = (uint32_t)H; l.W = (uint32_t)W;
+    l.bpp = hdr ? 2 : 1;
+    l.pitch_ya = (uint32_t)stride_a; l.pitch_yb = (uint32_t)stride_b;
+    l.pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a;
+    l.pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
+    l.base_ca = (size_t)H * (size_t)stride_a; l.base_cb = (size_t)H * (size_t)stride_b;
+    l.rows_c = planar ? 2u * (uint32_t)(H / 2) : (uint32_t)(H / 2);
+    l.elems_a = l.base_ca + (size_t)l.rows_c * l.pitch_ca; l.elems_b = l.base_cb + (size_t)l.rows_c * l.pitch_cb;
+    l.vec_y = (l.pitch_ya * l.bpp) % 16 == 0 && (l.pitch_yb * l.bpp) % 16 == 0;
+    for (int i = 0; i < n; i++)
+        if (((uintptr_t)a[i] | (uintptr_t)b[i]) & 15u) l.vec_y = 0;
+    l.vec_c = l.vec_y && (l.pitch_ca * l.bpp) % 16 == 0 && (l.pitch_cb * l.bpp) % 16 == 0;
+    return l;
+}
+
+// the pointer tables of a launch into its kernel arguments
+template <typename Args>
+void copy_pairs(Args& k, int n, const void* const* a, const void* const* b) {
+    k.n = n;
+    for (int i = 0; i < n; i++) { k.a[i] = a[i]; k.b[i] = b[i]; }
+}
+
+// what every pair of a launch shares and the pointer tables, into the arguments of the error kernel or of the error map kernel; false: n
+// out of range, or a frame beyond 2^32 work items
 template <typename Args>
 bool fill_error_args(Args& k, int hdr, int H, int W, int stride_a, int stride_b, bool planar, int n, const void* const* a, const void* const* b) {
-    if (n < 1 || n > kMaxErrorPairs) return false;
-    const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
+    const FrameLayout l = frame_layout(hdr, H, W, stride_a, stride_b, planar, n, a, b);
+    if (!l.ok) return false;
+    const uint32_t EL = 16 / l.bpp;
     ErrorShape& s = k.sh;
-    s.w_y = (uint32_t)W;
-    s.pitch_ya = (uint32_t)stride_a; s.pitch_yb = (uint32_t)stride_b;
-    const uint32_t rows_y = (uint32_t)H, rows_c = planar ? 2u * (uint32_t)(H / 2) : (uint32_t)(H / 2);
-    s.w_c = planar ? (uint32_t)(W / 2) : 2u * (uint32_t)(W / 2);
-    s.pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a;
-    s.pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
-    s.rows_u = (uint32_t)(H / 2);
-    s.base_ca = (size_t)H * (size_t)stride_a; s.base_cb = (size_t)H * (size_t)stride_b;
-    s.elems_a = s.base_ca + (size_t)rows_c * s.pitch_ca; s.elems_b = s.base_cb + (size_t)rows_c * s.pitch_cb;
+    s.w_y = l.W; s.w_c = planar ? l.W / 2 : 2u * (l.W / 2);
+    s.pitch_ya = l.pitch_ya; s.pitch_yb = l.pitch_yb; s.pitch_ca = l.pitch_ca; s.pitch_cb = l.pitch_cb;
+    s.rows_u = l.H / 2;
+    s.base_ca = l.base_ca; s.base_cb = l.base_cb; s.elems_a = l.elems_a; s.elems_b = l.elems_b;
     s.segs_y = (s.w_y + EL - 1) / EL; s.segs_c = (s.w_c + EL - 1) / EL;
-    const uint64_t items_y = (uint64_t)rows_y * s.segs_y, items_c = (uint64_t)rows_c * s.segs_c;
+    const uint64_t items_y = (uint64_t)l.H * s.segs_y, items_c = (uint64_t)l.rows_c * s.segs_c;
     if (items_y + (uint64_t)kErrMaxBlocks * kErrBlock >= (1ull << 32) || items_c + (uint64_t)kErrMaxBlocks * kErrBlock >= (1ull << 32)) return false;
     s.items_y = (uint32_t)items_y; s.items_c = (uint32_t)items_c;
     s.div_y = make_fastdiv(s.segs_y ? s.segs_y : 1u, items_y);
     s.div_c = make_fastdiv(s.segs_c ? s.segs_c : 1u, items_c);
-    // wide accesses: every row of every frame starts 16-byte aligned (the chroma base is a whole number of luma rows behind the frame's)
-    s.vec_y = (s.pitch_ya * bpp) % 16 == 0 && (s.pitch_yb * bpp) % 16 == 0;
-    s.vec_c = s.vec_y && (s.pitch_ca * bpp) % 16 == 0 && (s.pitch_cb * bpp) % 16 == 0;
-    k.n = n;
-    for (int i = 0; i < n; i++) {
-        k.a[i] = a[i]; k.b[i] = b[i];
-        if (!aligned16(a[i]) || !aligned16(b[i])) s.vec_y = s.vec_c = 0;
-    }
+    s.vec_y = l.vec_y; s.vec_c = l.vec_c;
+    copy_pairs(k, n, a, b);
     return true;
+}
+
+// plane i of a frame (0 luma; 1 interleaved UV, or U; 2 V) as both SSIM kernels see it, and the channels of its rows; tiles_x and
+// tile_first are the launcher's
+SsimPlane ssim_plane(const FrameLayout& l, int i, uint32_t* ch) {
+    const uint32_t w = i ? l.W / 2 : l.W, h = i ? l.H / 2 : l.H;
+    *ch = i && !l.planar ? 2u : 1u;
+    SsimPlane p{};
+    p.bw = w >> 2; p.bh = h >> 2; p.w_row = w * *ch;
+    p.pitch_a = i ? l.pitch_ca : l.pitch_ya; p.pitch_b = i ? l.pitch_cb : l.pitch_yb;
+    p.base_a = i ? l.base_ca + (i == 2 ? (size_t)h * l.pitch_ca : 0) : 0;
+    p.base_b = i ? l.base_cb + (i == 2 ? (size_t)h * l.pitch_cb : 0) : 0;
+    p.vec = i ? l.vec_c : l.vec_y;
+    return p;
+}
+
+// KERNEL<uint8_t | uint16_t, planar> of a launch
+#define HF_METRIC_KERNEL(KERNEL, hdr, planar) \
+    ((hdr) ? ((planar) ? KERNEL<uint16_t, true> : KERNEL<uint16_t, false>) : ((planar) ? KERNEL<uint8_t, true> : KERNEL<uint8_t, false>))
+
+// the workgroups of `block` lanes that the whole device holds of this kernel at once: a launch whose workgroups stride over their pair's
+// tiles wants no more (the rest would run in a second, mostly empty round).  Asked once per kernel (the same answer from every thread).
+template <typename Args>
+int resident_workgroups(void (*kernel)(const Args), int block, int hdr, bool planar) {
+    static int resident[2][2];   // by kernel of this Args
+    int& res = resident[hdr ? 1 : 0][planar ? 1 : 0];
+    if (!res) {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) { per_cu = 2; cus = 256; }
+        res = per_cu * cus;
+    }
+    return res;
 }
 
 }  // namespace
@@ -1004,13 +1030,7 @@ bool launch_frame_errors(int hdr, int H, int W, int stride_a, int stride_b, bool
     const size_t want = most ? (most + kErrBlock - 1) / kErrBlock : 1;
     const size_t cap = (size_t)kErrMaxBlocks / (size_t)n > 0 ? (size_t)kErrMaxBlocks / (size_t)n : 1;
     const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)n);
-    if (hdr) {
-        if (planar) HF_LAUNCH("frame_error", (frame_error_kernel<uint16_t, true>), grid, dim3(kErrBlock), 0, stream, k);
-        else        HF_LAUNCH("frame_error", (frame_error_kernel<uint16_t, false>), grid, dim3(kErrBlock), 0, stream, k);
-    } else {
-        if (planar) HF_LAUNCH("frame_error", (frame_error_kernel<uint8_t, true>), grid, dim3(kErrBlock), 0, stream, k);
-        else        HF_LAUNCH("frame_error", (frame_error_kernel<uint8_t, false>), grid, dim3(kErrBlock), 0, stream, k);
-    }
+    HF_LAUNCH("frame_error", HF_METRIC_KERNEL(frame_error_kernel, hdr, planar), grid, dim3(kErrBlock), 0, stream, k);
     return true;
 }
 
@@ -1030,66 +1050,33 @@ bool launch_frame_error_map(int hdr, int H, int W, int stride_a, int stride_b, b
     // a workgroup per band, in the order of the bands in memory; a launch of more than kMapMaxBlocks workgroups strides over them
     const uint32_t cap = (uint32_t)kMapMaxBlocks / (uint32_t)n;
     const dim3 grid(k.th < cap ? k.th : cap, (unsigned)n);
-    if (hdr) {
-        if (planar) HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint16_t, true>), grid, dim3(kMapBlock), 0, stream, k);
-        else        HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint16_t, false>), grid, dim3(kMapBlock), 0, stream, k);
-    } else {
-        if (planar) HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint8_t, true>), grid, dim3(kMapBlock), 0, stream, k);
-        else        HF_LAUNCH("frame_error_map", (frame_error_map_kernel<uint8_t, false>), grid, dim3(kMapBlock), 0, stream, k);
-    }
+    HF_LAUNCH("frame_error_map", HF_METRIC_KERNEL(frame_error_map_kernel, hdr, planar), grid, dim3(kMapBlock), 0, stream, k);
     return true;
 }
 
 bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int n, const void* const* a,
                        const void* const* b, FrameSsimSlot* slots, hipStream_t stream) {
-    if (n < 1 || n > kMaxErrorPairs) return false;
-    const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
+    const FrameLayout l = frame_layout(hdr, H, W, stride_a, stride_b, planar, n, a, b);
+    if (!l.ok) return false;
     SsimArgs k{};
     SsimShape& s = k.sh;
-    const uint32_t hc = (uint32_t)(H / 2), wc = (uint32_t)(W / 2);
-    const uint32_t pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a, pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
-    // wide accesses: as for the error sums (the chroma bases are whole numbers of rows behind the frame's)
-    int vec_y = ((uint32_t)stride_a * bpp) % 16 == 0 && ((uint32_t)stride_b * bpp) % 16 == 0;
-    for (int i = 0; i < n; i++) {
-        k.a[i] = a[i]; k.b[i] = b[i];
-        if (!aligned16(a[i]) || !aligned16(b[i])) vec_y = 0;
-    }
-    const int vec_c = vec_y && (pitch_ca * bpp) % 16 == 0 && (pitch_cb * bpp) % 16 == 0;
-    auto plane = [&](SsimPlane& p, uint32_t w, uint32_t h, uint32_t ch, size_t base_a, size_t base_b, uint32_t pitch_a, uint32_t pitch_b, int vec) {
-        p.bw = w >> 2; p.bh = h >> 2; p.w_row = w * ch;
-        p.pitch_a = pitch_a; p.pitch_b = pitch_b; p.base_a = base_a; p.base_b = base_b; p.vec = vec;
-        const uint32_t per_tile_x = (uint32_t)(kSsimUnitsX - 1) * (EL / 4 / ch), per_tile_y = (uint32_t)(kSsimRows - 1);   // windows
+    for (int i = 0; i < (planar ? 3 : 2); i++) {   // (interleaved: V comes with U, pl[2] stays empty)
+        uint32_t ch;
+        SsimPlane& p = s.pl[i] = ssim_plane(l, i, &ch);
+        const uint32_t per_tile_x = (uint32_t)(kSsimUnitsX - 1) * (16 / l.bpp / 4 / ch), per_tile_y = (uint32_t)(kSsimRows - 1);   // windows
         const bool any = p.bw > 1 && p.bh > 1;
         p.tiles_x = any ? (p.bw - 1 + per_tile_x - 1) / per_tile_x : 0;
         p.tile_first = s.tiles;
         s.tiles += any ? p.tiles_x * ((p.bh - 1 + per_tile_y - 1) / per_tile_y) : 0;
-    };
-    const size_t base_ca = (size_t)H * (size_t)stride_a, base_cb = (size_t)H * (size_t)stride_b;
-    plane(s.pl[0], (uint32_t)W, (uint32_t)H, 1, 0, 0, (uint32_t)stride_a, (uint32_t)stride_b, vec_y);
-    if (planar) {
-        plane(s.pl[1], wc, hc, 1, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
-        plane(s.pl[2], wc, hc, 1, base_ca + (size_t)hc * pitch_ca, base_cb + (size_t)hc * pitch_cb, pitch_ca, pitch_cb, vec_c);
-    } else {
-        plane(s.pl[1], wc, hc, 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
     }
-    const uint32_t rows_c = planar ? 2u * hc : hc;
-    s.elems_a = base_ca + (size_t)rows_c * pitch_ca; s.elems_b = base_cb + (size_t)rows_c * pitch_cb;
+    s.elems_a = l.elems_a; s.elems_b = l.elems_b;
     s.c1 = c1; s.c2 = c2;
-    k.n = n;
+    copy_pairs(k, n, a, b);
     k.slots = slots;
-    void (*kernel)(const SsimArgs) = hdr ? (planar ? frame_ssim_kernel<uint16_t, true> : frame_ssim_kernel<uint16_t, false>)
-                                         : (planar ? frame_ssim_kernel<uint8_t, true> : frame_ssim_kernel<uint8_t, false>);
-    // as many workgroups in the whole launch as the device holds at once (a workgroup strides over its pair's tiles: more would run in a
-    // second, mostly empty round), one at least per pair (a frame without a window: its slot stays zero)
-    static int resident[2][2];   // by kernel; asked once (the same answer from every thread)
-    int& res = resident[hdr ? 1 : 0][planar ? 1 : 0];
-    if (!res) {
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSsimBlock, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) { per_cu = 2; cus = 256; }
-        res = per_cu * cus;
-    }
-    const uint32_t cap = (uint32_t)res / (uint32_t)n > 0 ? (uint32_t)res / (uint32_t)n : 1u;
+    void (*kernel)(const SsimArgs) = HF_METRIC_KERNEL(frame_ssim_kernel, hdr, planar);
+    // as many workgroups in the whole launch as the device holds at once, one at least per pair (a frame without a window: its slot stays zero)
+    const uint32_t res = (uint32_t)resident_workgroups(kernel, kSsimBlock, hdr, planar);
+    const uint32_t cap = res / (uint32_t)n > 0 ? res / (uint32_t)n : 1u;
     const uint32_t want = s.tiles ? s.tiles : 1u;
     const dim3 grid(want < cap ? want : cap, (unsigned)n);
     if ((s.tiles + grid.x - 1) / grid.x >= kSsimMaxTilesPerWorkgroup) return false;   // (SsimLane; 2160p has 864 tiles)
@@ -1100,25 +1087,16 @@ bool launch_frame_ssim(int hdr, int H, int W, int stride_a, int stride_b, bool p
 // one SSIM map per pair into maps[i][3][th][tw] of hf_ssim_tile; tile 16, 32 or 64; every entry is stored by the launch
 bool launch_frame_ssim_map(int hdr, int H, int W, int stride_a, int stride_b, bool planar, long long c1, long long c2, int tile, int n,
                            const void* const* a, const void* const* b, void* maps, hipStream_t stream) {
-    if (n < 1 || n > kMaxErrorPairs || (tile != 16 && tile != 32 && tile != 64)) return false;
-    const uint32_t bpp = hdr ? 2 : 1, EL = 16 / bpp;
+    const FrameLayout l = frame_layout(hdr, H, W, stride_a, stride_b, planar, n, a, b);
+    if (!l.ok || (tile != 16 && tile != 32 && tile != 64)) return false;
     SmapArgs k{};
     k.tw = ((uint32_t)W + (uint32_t)tile - 1) / (uint32_t)tile; k.th = ((uint32_t)H + (uint32_t)tile - 1) / (uint32_t)tile;
-    const uint32_t hc = (uint32_t)(H / 2), wc = (uint32_t)(W / 2);
-    const uint32_t pitch_ca = planar ? (uint32_t)(stride_a / 2) : (uint32_t)stride_a, pitch_cb = planar ? (uint32_t)(stride_b / 2) : (uint32_t)stride_b;
-    // wide accesses: as for the error sums (the chroma bases are whole numbers of rows behind the frame's)
-    int vec_y = ((uint32_t)stride_a * bpp) % 16 == 0 && ((uint32_t)stride_b * bpp) % 16 == 0;
-    for (int i = 0; i < n; i++) {
-        k.a[i] = a[i]; k.b[i] = b[i];
-        if (!aligned16(a[i]) || !aligned16(b[i])) vec_y = 0;
-    }
-    const int vec_c = vec_y && (pitch_ca * bpp) % 16 == 0 && (pitch_cb * bpp) % 16 == 0;
-    auto plane = [&](SmapPlane& m, uint32_t w, uint32_t h, uint32_t ch, uint32_t te, size_t base_a, size_t base_b, uint32_t pitch_a, uint32_t pitch_b, int vec) {
-        SsimPlane& p = m.p;
-        p.bw = w >> 2; p.bh = h >> 2; p.w_row = w * ch;
-        p.pitch_a = pitch_a; p.pitch_b = pitch_b; p.base_a = base_a; p.base_b = base_b; p.vec = vec;
-        const uint32_t bpu = EL / 4 / ch;                   // blocks of a channel in a unit: 1, 2 or 4
-        m.tb = te / 4;                                      // 2 .. 16
+    for (int i = 0; i < (planar ? 3 : 2); i++) {
+        uint32_t ch;
+        SmapPlane& m = k.pl[i];
+        SsimPlane& p = m.p = ssim_plane(l, i, &ch);
+        const uint32_t bpu = 16 / l.bpp / 4 / ch;           // blocks of a channel in a unit: 1, 2 or 4
+        m.tb = (uint32_t)(i ? tile / 2 : tile) / 4;         // 2 .. 16
         m.lg_tb = m.tb >= 16 ? 4u : m.tb >= 8 ? 3u : m.tb >= 4 ? 2u : 1u;
         m.halves = m.tb < bpu;                              // (tb 2, bpu 4)
         const uint32_t tu = m.halves ? 1u : m.tb / bpu;     // 1, 2, 4 or 8
@@ -1128,39 +1106,22 @@ bool launch_frame_ssim_map(int hdr, int H, int W, int stride_a, int stride_b, bo
         p.tiles_x = (k.tw + tiles_across - 1) / tiles_across;
         p.tile_first = k.patches;
         k.patches += p.tiles_x * ((k.th + tiles_down - 1) / tiles_down);
-    };
-    const size_t base_ca = (size_t)H * (size_t)stride_a, base_cb = (size_t)H * (size_t)stride_b;
-    const uint32_t te = (uint32_t)tile;
-    plane(k.pl[0], (uint32_t)W, (uint32_t)H, 1, te, 0, 0, (uint32_t)stride_a, (uint32_t)stride_b, vec_y);
-    if (planar) {
-        plane(k.pl[1], wc, hc, 1, te / 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
-        plane(k.pl[2], wc, hc, 1, te / 2, base_ca + (size_t)hc * pitch_ca, base_cb + (size_t)hc * pitch_cb, pitch_ca, pitch_cb, vec_c);
-    } else {
-        plane(k.pl[1], wc, hc, 2, te / 2, base_ca, base_cb, pitch_ca, pitch_cb, vec_c);
-        k.pl[2] = k.pl[1]; k.pl[2].p.tile_first = k.patches;   // (no patch of its own: V comes with U)
     }
-    const uint32_t rows_c = planar ? 2u * hc : hc;
-    k.elems_a = base_ca + (size_t)rows_c * pitch_ca; k.elems_b = base_cb + (size_t)rows_c * pitch_cb;
+    if (!planar) { k.pl[2] = k.pl[1]; k.pl[2].p.tile_first = k.patches; }   // (no patch of its own: V comes with U)
+    k.elems_a = l.elems_a; k.elems_b = l.elems_b;
     k.entries = (size_t)n * 3u * k.th * k.tw;
     k.c1 = c1; k.c2 = c2;
-    k.n = n;
+    copy_pairs(k, n, a, b);
     k.maps = static_cast<SsimTileOut*>(maps);
-    void (*kernel)(const SmapArgs) = hdr ? (planar ? frame_ssim_map_kernel<uint16_t, true> : frame_ssim_map_kernel<uint16_t, false>)
-                                         : (planar ? frame_ssim_map_kernel<uint8_t, true> : frame_ssim_map_kernel<uint8_t, false>);
+    void (*kernel)(const SmapArgs) = HF_METRIC_KERNEL(frame_ssim_map_kernel, hdr, planar);
     // as many workgroups in the whole launch as the device holds at once, one at least per pair: a workgroup strides over its pair's patches
-    static int resident[2][2];   // by kernel; asked once (the same answer from every thread)
-    int& res = resident[hdr ? 1 : 0][planar ? 1 : 0];
-    if (!res) {
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSmapBlock, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) { per_cu = 2; cus = 256; }
-        res = per_cu * cus;
-    }
-    const uint32_t cap = (uint32_t)res / (uint32_t)n > 0 ? (uint32_t)res / (uint32_t)n : 1u;
+    const uint32_t res = (uint32_t)resident_workgroups(kernel, kSmapBlock, hdr, planar);
+    const uint32_t cap = res / (uint32_t)n > 0 ? res / (uint32_t)n : 1u;
     const dim3 grid(k.patches < cap ? k.patches : cap, (unsigned)n);
     HF_LAUNCH("frame_ssim_map", kernel, grid, dim3(kSmapBlock), 0, stream, k);
     return true;
 }
+#undef HF_METRIC_KERNEL
 
 bool dbg_bounds_read_metrics(unsigned out[5], bool reset) {
 #ifdef HF_DEBUG_BOUNDS
@@ -1193,35 +1154,6 @@ static int check_pairs(hf_ctx* c, const char* who, int n, const void* const* a, 
     return HF_OK;
 }
 
-// slots [first, first + n) zeroed, then pair i compared into slot first + i -- behind everything the context has enqueued: warps on a
-// second stream (HF_FLAG_DUAL_STREAM) are waited for like hf_download_frame_device does, a batch member issues on the batch's stream.
-// max_slot: HF_ERROR_SLOTS for the public range, one more for hf_frame_error's own slot.
-static int enqueue_errors(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar,
-                          int first_slot, int max_slot) {
-    HF_CHECK_CTX(c);
-    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, HF_ERROR_SLOTS)) return rc;
-    if (int rc = set_device(c)) return rc;
-    if (!c->error_slots) HF_HIP(c, alloc_device(c->error_slots, (size_t)(HF_ERROR_SLOTS + 1) * sizeof(hf::FrameErrorSlot)));
-    if (int rc = leave_warp_stream(c)) return rc;
-    hf::FrameErrorSlot* slots = c->error_slots.get() + first_slot;
-    HF_HIP(c, hipMemsetAsync(slots, 0, (size_t)n * sizeof(hf::FrameErrorSlot), c->stream));
-    if (!hf::launch_frame_errors(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, n, a, b, slots, c->stream))
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
-    HF_HIP(c, hipGetLastError());
-    return HF_OK;
-}
-
-static int read_errors(hf_ctx* c, int first_slot, int n, int max_slot, struct hf_frame_error* out) {
-    HF_CHECK_CTX(c);
-    if (!out || n < 1 || first_slot < 0 || first_slot > max_slot - n)
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_error_read: slots [%d, %d + %d) outside [0, %d), or null", first_slot, first_slot, n, HF_ERROR_SLOTS);
-    if (!c->error_slots) return fail(c, HF_ERR_STATE, "hf_frame_error_read: nothing was enqueued");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = leave_warp_stream(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(out, c->error_slots.get() + first_slot, (size_t)n * sizeof(struct hf_frame_error), hipMemcpyDeviceToHost, c->stream));
-    return sync_ctx(c);
-}
-
 // the peak rule and the integer constants of the SSIM calls (hopperflow.h, step 3); refuses a peak outside its range
 static int ssim_constants(hf_ctx* c, const char* who, int planar, int peak, long long* c1, long long* c2) {
     const int top = c->g.hdr ? 65535 : 255;
@@ -1231,35 +1163,98 @@ static int ssim_constants(hf_ctx* c, const char* who, int planar, int peak, long
     return HF_OK;
 }
 
-// The windowed SSIM of the same pairs into slots of its own: ordered, refused and read like the error sums.  peak 0: the format's own.
-static int enqueue_ssim(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar, int peak,
-                        int first_slot, int max_slot) {
+// The two families of result slots -- error sums, and the windowed SSIM of the same pairs in slots of its own -- go through ONE enqueue
+// and ONE read.  A family: the context's buffer of n_slots public slots and one more for the blocking call, the read call's name, and
+// whether a fresh buffer is zeroed whole (the SSIM slots: one never used reads as zeros; the error slots are not, as they never were).
+template <typename Slot>
+struct SlotFamily {
+    DevBuf<Slot> hf_ctx::*buf;
+    int n_slots;
+    const char* read_name;
+    bool zero_fresh;
+};
+static constexpr SlotFamily<hf::FrameErrorSlot> kErrorSlots{&hf_ctx::error_slots, HF_ERROR_SLOTS, "hf_frame_error_read", false};
+static constexpr SlotFamily<hf::FrameSsimSlot> kSsimSlots{&hf_ctx::ssim_slots, HF_SSIM_SLOTS, "hf_frame_ssim_read", true};
+
+// slots [first, first + n) zeroed, then pair i measured into slot first + i by launch(slots, c1, c2) -- behind everything the context has
+// enqueued: warps on a second stream (HF_FLAG_DUAL_STREAM) are waited for like hf_download_frame_device does, a batch member issues on the
+// batch's stream.  max_slot: n_slots for the public range, one more for the blocking call's own slot.  peak: of the SSIM calls, whose
+// constants are settled between the checks of the pairs and the first use of the device; null for the error sums.
+template <typename Slot, typename Launch>
+static int enqueue_slots(hf_ctx* c, const SlotFamily<Slot>& fam, const char* who, int n, const void* const* a, const void* const* b, int stride_a,
+                         int stride_b, int planar, const int* peak, int first_slot, int max_slot, Launch launch) {
     HF_CHECK_CTX(c);
-    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, HF_SSIM_SLOTS)) return rc;
-    long long c1, c2;
-    if (int rc = ssim_constants(c, who, planar, peak, &c1, &c2)) return rc;
+    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, first_slot, max_slot, fam.n_slots)) return rc;
+    long long c1 = 0, c2 = 0;
+    if (peak)
+        if (int rc = ssim_constants(c, who, planar, *peak, &c1, &c2)) return rc;
     if (int rc = set_device(c)) return rc;
-    const bool fresh = !c->ssim_slots;
-    if (fresh) HF_HIP(c, alloc_device(c->ssim_slots, (size_t)(HF_SSIM_SLOTS + 1) * sizeof(hf::FrameSsimSlot)));
+    DevBuf<Slot>& buf = c->*fam.buf;
+    const size_t all = (size_t)(fam.n_slots + 1) * sizeof(Slot);
+    const bool fresh = !buf;
+    if (fresh) HF_HIP(c, alloc_device(buf, all));
     if (int rc = leave_warp_stream(c)) return rc;
-    if (fresh) HF_HIP(c, hipMemsetAsync(c->ssim_slots.get(), 0, (size_t)(HF_SSIM_SLOTS + 1) * sizeof(hf::FrameSsimSlot), c->stream));   // a slot never used reads as zeros
-    hf::FrameSsimSlot* slots = c->ssim_slots.get() + first_slot;
-    HF_HIP(c, hipMemsetAsync(slots, 0, (size_t)n * sizeof(hf::FrameSsimSlot), c->stream));
-    if (!hf::launch_frame_ssim(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, n, a, b, slots, c->stream))
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
+    if (fresh && fam.zero_fresh) HF_HIP(c, hipMemsetAsync(buf.get(), 0, all, c->stream));
+    Slot* slots = buf.get() + first_slot;
+    HF_HIP(c, hipMemsetAsync(slots, 0, (size_t)n * sizeof(Slot), c->stream));
+    if (!launch(slots, c1, c2)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
     HF_HIP(c, hipGetLastError());
     return HF_OK;
 }
 
-static int read_ssim(hf_ctx* c, int first_slot, int n, int max_slot, struct hf_frame_ssim* out) {
+template <typename Slot, typename Out>
+static int read_slots(hf_ctx* c, const SlotFamily<Slot>& fam, int first_slot, int n, int max_slot, Out* out) {
+    static_assert(sizeof(Out) == sizeof(Slot), "a slot is its public struct");
     HF_CHECK_CTX(c);
     if (!out || n < 1 || first_slot < 0 || first_slot > max_slot - n)
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_ssim_read: slots [%d, %d + %d) outside [0, %d), or null", first_slot, first_slot, n, HF_SSIM_SLOTS);
-    if (!c->ssim_slots) return fail(c, HF_ERR_STATE, "hf_frame_ssim_read: nothing was enqueued");
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: slots [%d, %d + %d) outside [0, %d), or null", fam.read_name, first_slot, first_slot, n, fam.n_slots);
+    if (!(c->*fam.buf)) return fail(c, HF_ERR_STATE, "%s: nothing was enqueued", fam.read_name);
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
-    HF_HIP(c, hipMemcpyAsync(out, c->ssim_slots.get() + first_slot, (size_t)n * sizeof(struct hf_frame_ssim), hipMemcpyDeviceToHost, c->stream));
+    HF_HIP(c, hipMemcpyAsync(out, (c->*fam.buf).get() + first_slot, (size_t)n * sizeof(Out), hipMemcpyDeviceToHost, c->stream));
     return sync_ctx(c);
+}
+
+static int enqueue_errors(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar,
+                          int first_slot, int max_slot) {
+    return enqueue_slots(c, kErrorSlots, who, n, a, b, stride_a, stride_b, planar, nullptr, first_slot, max_slot, [&](hf::FrameErrorSlot* slots, long long, long long) {
+        return hf::launch_frame_errors(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, n, a, b, slots, c->stream);
+    });
+}
+
+static int enqueue_ssim(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar, int peak,
+                        int first_slot, int max_slot) {
+    return enqueue_slots(c, kSsimSlots, who, n, a, b, stride_a, stride_b, planar, &peak, first_slot, max_slot, [&](hf::FrameSsimSlot* slots, long long c1, long long c2) {
+        return hf::launch_frame_ssim(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, n, a, b, slots, c->stream);
+    });
+}
+
+// The two kinds of per-tile maps share the tile grid; an entry is `entry` bytes
+static int map_shape(const hf_ctx* c, int tile, size_t entry, int* tiles_x, int* tiles_y, size_t* bytes_per_map) {
+    if (!c || !HF_ERROR_MAP_TILES_OK(tile)) return HF_ERR_INVALID_ARGUMENT;
+    const int tw = (c->g.W + tile - 1) / tile, th = (c->g.H + tile - 1) / tile;
+    if (tiles_x) *tiles_x = tw;
+    if (tiles_y) *tiles_y = th;
+    if (bytes_per_map) *bytes_per_map = 3 * entry * (size_t)tw * (size_t)th;
+    return HF_OK;
+}
+
+// ... and one enqueue, ordered like enqueue_slots; no slots, no memset: launch(c1, c2) stores every entry of the caller's buffer
+template <typename Launch>
+static int enqueue_map(hf_ctx* c, const char* who, int n, const void* const* a, const void* const* b, int stride_a, int stride_b, int planar,
+                       const int* peak, int tile, void* device_maps, Launch launch) {
+    HF_CHECK_CTX(c);
+    if (int rc = check_pairs(c, who, n, a, b, stride_a, stride_b, planar, 0, n, n)) return rc;
+    long long c1 = 0, c2 = 0;
+    if (peak)
+        if (int rc = ssim_constants(c, who, planar, *peak, &c1, &c2)) return rc;
+    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
+    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    if (!launch(c1, c2)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
+    HF_HIP(c, hipGetLastError());
+    return HF_OK;
 }
 
 extern "C" {
@@ -1269,38 +1264,24 @@ int hf_frame_error_enqueue(hf_ctx* c, int n, const void* const* device_a, const 
     return enqueue_errors(c, "hf_frame_error_enqueue", n, device_a, device_b, stride_a, stride_b, planar, first_slot, HF_ERROR_SLOTS);
 }
 
-int hf_frame_error_read(hf_ctx* c, int first_slot, int n, struct hf_frame_error* out) { return read_errors(c, first_slot, n, HF_ERROR_SLOTS, out); }
+int hf_frame_error_read(hf_ctx* c, int first_slot, int n, struct hf_frame_error* out) { return read_slots(c, kErrorSlots, first_slot, n, HF_ERROR_SLOTS, out); }
 
 int hf_frame_error(hf_ctx* c, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar, struct hf_frame_error* out) {
     HF_CHECK_CTX(c);
     if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_error: null result");
     if (int rc = enqueue_errors(c, "hf_frame_error", 1, &device_a, &device_b, stride_a, stride_b, planar, HF_ERROR_SLOTS, HF_ERROR_SLOTS + 1)) return rc;
-    return read_errors(c, HF_ERROR_SLOTS, 1, HF_ERROR_SLOTS + 1, out);
+    return read_slots(c, kErrorSlots, HF_ERROR_SLOTS, 1, HF_ERROR_SLOTS + 1, out);
 }
 
 int hf_frame_error_map_shape(const hf_ctx* c, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map) {
-    if (!c || !HF_ERROR_MAP_TILES_OK(tile)) return HF_ERR_INVALID_ARGUMENT;
-    const int tw = (c->g.W + tile - 1) / tile, th = (c->g.H + tile - 1) / tile;
-    if (tiles_x) *tiles_x = tw;
-    if (tiles_y) *tiles_y = th;
-    if (bytes_per_map) *bytes_per_map = 3 * sizeof(struct hf_error_tile) * (size_t)tw * (size_t)th;
-    return HF_OK;
+    return map_shape(c, tile, sizeof(struct hf_error_tile), tiles_x, tiles_y, bytes_per_map);
 }
 
-// ordered like enqueue_errors; no slots, no memset: the launch stores every entry of the caller's buffer
 int hf_frame_error_map_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
                                int tile, void* device_maps) {
-    const char* who = "hf_frame_error_map_enqueue";
-    HF_CHECK_CTX(c);
-    if (int rc = check_pairs(c, who, n, device_a, device_b, stride_a, stride_b, planar, 0, n, n)) return rc;
-    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
-    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = leave_warp_stream(c)) return rc;
-    if (!hf::launch_frame_error_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, tile, n, device_a, device_b, device_maps, c->stream))
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
-    HF_HIP(c, hipGetLastError());
-    return HF_OK;
+    return enqueue_map(c, "hf_frame_error_map_enqueue", n, device_a, device_b, stride_a, stride_b, planar, nullptr, tile, device_maps, [&](long long, long long) {
+        return hf::launch_frame_error_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, tile, n, device_a, device_b, device_maps, c->stream);
+    });
 }
 
 int hf_frame_ssim_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
@@ -1308,40 +1289,24 @@ int hf_frame_ssim_enqueue(hf_ctx* c, int n, const void* const* device_a, const v
     return enqueue_ssim(c, "hf_frame_ssim_enqueue", n, device_a, device_b, stride_a, stride_b, planar, peak, first_slot, HF_SSIM_SLOTS);
 }
 
-int hf_frame_ssim_read(hf_ctx* c, int first_slot, int n, struct hf_frame_ssim* out) { return read_ssim(c, first_slot, n, HF_SSIM_SLOTS, out); }
+int hf_frame_ssim_read(hf_ctx* c, int first_slot, int n, struct hf_frame_ssim* out) { return read_slots(c, kSsimSlots, first_slot, n, HF_SSIM_SLOTS, out); }
 
 int hf_frame_ssim(hf_ctx* c, const void* device_a, const void* device_b, int stride_a, int stride_b, int planar, int peak, struct hf_frame_ssim* out) {
     HF_CHECK_CTX(c);
     if (!out) return fail(c, HF_ERR_INVALID_ARGUMENT, "hf_frame_ssim: null result");
     if (int rc = enqueue_ssim(c, "hf_frame_ssim", 1, &device_a, &device_b, stride_a, stride_b, planar, peak, HF_SSIM_SLOTS, HF_SSIM_SLOTS + 1)) return rc;
-    return read_ssim(c, HF_SSIM_SLOTS, 1, HF_SSIM_SLOTS + 1, out);
+    return read_slots(c, kSsimSlots, HF_SSIM_SLOTS, 1, HF_SSIM_SLOTS + 1, out);
 }
 
 int hf_frame_ssim_map_shape(const hf_ctx* c, int tile, int* tiles_x, int* tiles_y, size_t* bytes_per_map) {
-    if (!c || !HF_ERROR_MAP_TILES_OK(tile)) return HF_ERR_INVALID_ARGUMENT;
-    const int tw = (c->g.W + tile - 1) / tile, th = (c->g.H + tile - 1) / tile;
-    if (tiles_x) *tiles_x = tw;
-    if (tiles_y) *tiles_y = th;
-    if (bytes_per_map) *bytes_per_map = 3 * sizeof(struct hf_ssim_tile) * (size_t)tw * (size_t)th;
-    return HF_OK;
+    return map_shape(c, tile, sizeof(struct hf_ssim_tile), tiles_x, tiles_y, bytes_per_map);
 }
 
-// ordered like enqueue_errors; no slots, no memset: the launch stores every entry of the caller's buffer
 int hf_frame_ssim_map_enqueue(hf_ctx* c, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b, int planar,
                               int peak, int tile, void* device_maps) {
-    const char* who = "hf_frame_ssim_map_enqueue";
-    HF_CHECK_CTX(c);
-    if (int rc = check_pairs(c, who, n, device_a, device_b, stride_a, stride_b, planar, 0, n, n)) return rc;
-    long long c1, c2;
-    if (int rc = ssim_constants(c, who, planar, peak, &c1, &c2)) return rc;
-    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
-    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = leave_warp_stream(c)) return rc;
-    if (!hf::launch_frame_ssim_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, tile, n, device_a, device_b, device_maps, c->stream))
-        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the frame is too large for one launch", who);
-    HF_HIP(c, hipGetLastError());
-    return HF_OK;
+    return enqueue_map(c, "hf_frame_ssim_map_enqueue", n, device_a, device_b, stride_a, stride_b, planar, &peak, tile, device_maps, [&](long long c1, long long c2) {
+        return hf::launch_frame_ssim_map(c->g.hdr, c->g.H, c->g.W, stride_a, stride_b, planar != 0, c1, c2, tile, n, device_a, device_b, device_maps, c->stream);
+    });
 }
 
 }  // extern "C"

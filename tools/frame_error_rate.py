@@ -8,74 +8,24 @@ and 1 GB of them, so nothing is served from the 256 MB cache -- between the libr
 same process, before and after.  The probe reports read + write bytes per second; the kernel only reads, 2 F bytes per pair.
 Prints one JSON object.
 """
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-
-from hopperrender_amd import capi  # noqa: E402
-from hopperrender_amd.calc import DeviceBuffer, OpticalFlowCalcHDR, OpticalFlowCalcSDR  # noqa: E402
-
-CASES = (("2160p_hdr_60_pairs", 2160, 3840, True, 60), ("1080p_sdr_160_pairs", 1080, 1920, False, 160))
-
-
-def probe():
-    g = C.c_double()
-    capi.check(capi.load().hf_hbm_copy_probe(0, 512 << 20, 5, C.byref(g)))
-    return g.value
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from metrics_rate_common import finish, parse_args, rates, run, timed  # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--launches", type=int, default=40); ap.add_argument("--readings", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    res = {"hbm_copy_probe_GBps_before": round(probe(), 1)}
-    for name, H, W, hdr, n in CASES:
-        c = (OpticalFlowCalcHDR if hdr else OpticalFlowCalcSDR)(H, W, flags=capi.HF_FLAG_ASYNC)
-        nb = int(c.input_frame_bytes)
-        rng = np.random.default_rng(1)
-        host = [rng.integers(0, 256, nb, dtype=np.uint8) for _ in range(2)]
-        fa, fb = [DeviceBuffer(nb) for _ in range(n)], [DeviceBuffer(nb) for _ in range(n)]
-        for x in fa:
-            x.upload(host[0])
-        for x in fb:
-            x.upload(host[1])
-        pa, pb = [x.ptr for x in fa], [x.ptr for x in fb]
-        for _ in range(3):
-            c.frameErrorEnqueue(pa, pb, 0)
-        c.sync()
-        us = []
-        for _ in range(a.readings):
-            c.timerBegin()
-            for _ in range(a.launches):
-                c.frameErrorEnqueue(pa, pb, 0)
-            us.append(c.timerEnd() * 1e3 / a.launches)
+    a = parse_args(__doc__)
+
+    def case(fr, H, W, n):
+        c = fr.c
+        us = timed(c, {"frame_error": lambda: c.frameErrorEnqueue(fr.pa, fr.pb, 0)}, a.launches, a.readings)
         got = c.frameErrorRead(0, 1)[0]
         assert got["Y"]["count"] == H * W and got["U"]["count"] == H * W // 4, got
-        us.sort()
-        rate = lambda t: 2 * nb * n / (t * 1e-6) / 1e9
-        res[name] = {"pairs": n, "bytes_read": 2 * nb * n, "us_per_launch_best": round(us[0], 1), "us_per_launch_median": round(us[len(us) // 2], 1),
-                     "us_per_pair_median": round(us[len(us) // 2] / n, 3), "GBps_read_best": round(rate(us[0]), 1),
-                     "GBps_read_median": round(rate(us[len(us) // 2]), 1), "pairs_per_s_median": round(n / (us[len(us) // 2] * 1e-6))}
-        for x in fa + fb:
-            x.free()
-        c.close()
-    res["hbm_copy_probe_GBps_after"] = round(probe(), 1)
-    pr = max(res["hbm_copy_probe_GBps_before"], res["hbm_copy_probe_GBps_after"])
-    for name, *_ in CASES:
-        res[name]["share_of_copy_probe"] = round(res[name]["GBps_read_median"] / pr, 3)
-    s = json.dumps(res, indent=1)
-    print(s)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+        return rates(us["frame_error"], fr.nb, n)
+
+    finish(run(case), lambda r: [r], a.out)
 
 
 if __name__ == "__main__":

@@ -10,85 +10,27 @@ warm-up, the median of `--readings` readings; this box's streaming-copy probe (h
 second.  Prints one JSON object: per case and kernel the microseconds per launch, bytes read per second and the share of the probe, and
 the ratio of SSIM time to error time.
 """
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-
-from hopperrender_amd import capi  # noqa: E402
-from hopperrender_amd.calc import DeviceBuffer, OpticalFlowCalcHDR, OpticalFlowCalcSDR  # noqa: E402
-
-CASES = (("2160p_hdr_60_pairs", 2160, 3840, True, 60), ("1080p_sdr_160_pairs", 1080, 1920, False, 160))
-
-
-def probe():
-    g = C.c_double()
-    capi.check(capi.load().hf_hbm_copy_probe(0, 512 << 20, 5, C.byref(g)))
-    return g.value
-
-
-def timed(c, enqueue, launches, readings):
-    """sorted microseconds per launch of `readings` readings of `launches` back-to-back launches"""
-    for _ in range(3):
-        enqueue()
-    c.sync()
-    us = []
-    for _ in range(readings):
-        c.timerBegin()
-        for _ in range(launches):
-            enqueue()
-        us.append(c.timerEnd() * 1e3 / launches)
-    return sorted(us)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from metrics_rate_common import finish, parse_args, rates, run, timed  # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--launches", type=int, default=40); ap.add_argument("--readings", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    res = {"hbm_copy_probe_GBps_before": round(probe(), 1)}
-    for name, H, W, hdr, n in CASES:
-        c = (OpticalFlowCalcHDR if hdr else OpticalFlowCalcSDR)(H, W, flags=capi.HF_FLAG_ASYNC)
-        nb = int(c.input_frame_bytes)
-        rng = np.random.default_rng(1)
-        host = [rng.integers(0, 256, nb, dtype=np.uint8) for _ in range(2)]
-        fa, fb = [DeviceBuffer(nb) for _ in range(n)], [DeviceBuffer(nb) for _ in range(n)]
-        for x in fa:
-            x.upload(host[0])
-        for x in fb:
-            x.upload(host[1])
-        pa, pb = [x.ptr for x in fa], [x.ptr for x in fb]
-        rate = lambda t: 2 * nb * n / (t * 1e-6) / 1e9
-        res[name] = {"pairs": n, "bytes_read": 2 * nb * n}
-        for kernel, enqueue in (("frame_error", lambda: c.frameErrorEnqueue(pa, pb, 0)), ("frame_ssim", lambda: c.frameSsimEnqueue(pa, pb, 0))):
-            us = timed(c, enqueue, a.launches, a.readings)
-            med = us[len(us) // 2]
-            res[name][kernel] = {"us_per_launch_best": round(us[0], 1), "us_per_launch_median": round(med, 1), "us_per_pair_median": round(med / n, 3),
-                                 "GBps_read_best": round(rate(us[0]), 1), "GBps_read_median": round(rate(med), 1), "pairs_per_s_median": round(n / (med * 1e-6))}
-        res[name]["ssim_over_error_median"] = round(res[name]["frame_ssim"]["us_per_launch_median"] / res[name]["frame_error"]["us_per_launch_median"], 3)
+    a = parse_args(__doc__)
+
+    def case(fr, H, W, n):
+        c = fr.c
+        enqueues = {"frame_error": lambda: c.frameErrorEnqueue(fr.pa, fr.pb, 0), "frame_ssim": lambda: c.frameSsimEnqueue(fr.pa, fr.pb, 0)}
+        r = {k: rates(us, fr.nb, n) for k, us in timed(c, enqueues, a.launches, a.readings).items()}
+        r["ssim_over_error_median"] = round(r["frame_ssim"]["us_per_launch_median"] / r["frame_error"]["us_per_launch_median"], 3)
         err, ssim = c.frameErrorRead(0, 1)[0], c.frameSsimRead(0, 1)[0]
         assert err["Y"]["count"] == H * W and err["U"]["count"] == H * W // 4, err
         assert ssim["Y"]["count"] == (W // 4 - 1) * (H // 4 - 1) and ssim["U"]["count"] == (W // 8 - 1) * (H // 8 - 1) and ssim["Y"]["sum_loss_q32"] > 0, ssim
-        for x in fa + fb:
-            x.free()
-        c.close()
-    res["hbm_copy_probe_GBps_after"] = round(probe(), 1)
-    pr = max(res["hbm_copy_probe_GBps_before"], res["hbm_copy_probe_GBps_after"])
-    for name, *_ in CASES:
-        for kernel in ("frame_error", "frame_ssim"):
-            res[name][kernel]["share_of_copy_probe"] = round(res[name][kernel]["GBps_read_median"] / pr, 3)
-    s = json.dumps(res, indent=1)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+        return r
+
+    finish(run(case), lambda r: [r["frame_error"], r["frame_ssim"]], a.out)
 
 
 if __name__ == "__main__":
