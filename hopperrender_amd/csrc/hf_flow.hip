@@ -1442,9 +1442,7 @@ __global__ void expand_offsets_kernel(const Geom g, const FlowLevel L, int16_t* 
 template <typename E>
 static bool launch_prep_fast(const Geom& g, const PhaseLayout& pl, const PrepBatch& b, hipStream_t stream) {
     const int lw = g.W >> g.rs;
-    const size_t row_bytes = (size_t)g.in_stride * sizeof(E);
-    if ((lw << g.rs) != g.W || lw != g.lw || (lw & 3) || pl.mx > lw || (pl.mx & 3) || (row_bytes & 15) || (pl.lwp & 3) || g.rs > 4 || (g.H & 1))
-        return false;
+    if (!plane_fast_geometry(g, pl)) return false;    // (hf_launch_plan.h; E is g's element type)
     for (int i = 0; i < b.n; i++) if (((uintptr_t)b.frame[i]) & 15) return false;
     const dim3 grd((lw / 4 + 127) / 128, g.H / 2, b.n);
     const bool nt = b.n > 1;     // batches: non-temporal plane stores (hf_phase_plane.h); a single context's plane stays in the caches for its chain

@@ -147,13 +147,18 @@ inline long warp_n_tiles(const Geom& g, int vb) {   // wave tiles of a frame, bo
     return (long)warp_tiles_per_row(g, vb) * (warp_tile_rows(g.H, kWarpFastRows) + warp_tile_rows(g.H >> 1, kWarpFastRows));
 }
 inline bool staged_rounds(long n_tiles, int members) { return n_tiles * members >= kWgMinWaves; }
-// Can the staged kernel build the phase planes of its members' frame21 (emit_plane_rows)?  The geometry part of the answer
-// (= the conditions of the fast plane kernel, hf_flow.hip launch_prep_fast).
-inline bool plane_emission_geometry(const Geom& g, const PhaseLayout& pl) {
-    const size_t esz = elem_size(g);
+// Does the fast plane build (hf_phase_plane.h plane_fast_task) apply to frames of this geometry?  Whole grid columns (W == lw << rs), tasks
+// of 4 columns, margins one reflection deep at most and in whole tasks, 16-byte task loads and stores, an instantiated rs, whole chroma
+// rows.  The geometry part of hf_flow.hip launch_prep_fast's answer: the 16-byte alignment of each frame's base is the launch's own test.
+inline bool plane_fast_geometry(const Geom& g, const PhaseLayout& pl) {
     const int lw = g.W >> g.rs;
-    return g.rs >= 3 && g.rs <= 4 && pl.rs == g.rs && (lw << g.rs) == g.W && lw == g.lw && (lw & 3) == 0 && pl.mx <= lw && (pl.mx & 3) == 0 &&
-           (pl.lwp & 3) == 0 && ((size_t)g.in_stride * esz) % 16 == 0 && ((size_t)g.H * g.in_stride * esz) % 16 == 0 && (g.H & 1) == 0;
+    return (lw << g.rs) == g.W && lw == g.lw && (lw & 3) == 0 && pl.mx <= lw && (pl.mx & 3) == 0 && (pl.lwp & 3) == 0 &&
+           ((size_t)g.in_stride * elem_size(g)) % 16 == 0 && g.rs <= 4 && (g.H & 1) == 0;
+}
+// Can the staged kernel build the phase planes of its members' frame21 (emit_plane_rows)?  The geometry part of the answer: the two
+// instantiations of its tasks, a chroma plane that starts on a 16-byte boundary, and the conditions of the fast plane build.
+inline bool plane_emission_geometry(const Geom& g, const PhaseLayout& pl) {
+    return g.rs >= 3 && g.rs <= 4 && pl.rs == g.rs && ((size_t)g.H * g.in_stride * elem_size(g)) % 16 == 0 && plane_fast_geometry(g, pl);
 }
 
 // Static part of the deferred-plane decision for a batch of n_members contexts of geometry g (hf_batch decides once whether it defers

@@ -68,6 +68,13 @@ void hfp_phase_layout(const int* gv, int max_iters, long long* o) {
     o[0] = pl.rs; o[1] = pl.nph; o[2] = pl.nph2; o[3] = pl.mx; o[4] = pl.lwp; o[5] = (long long)pl.bytes;
 }
 
+// o[0]: the fast plane build applies to frames of this geometry (their bases' alignment aside); o[1]: the staged warp launch can build planes
+void hfp_plane_fast_geometry(const int* gv, int max_iters, long long* o) {
+    const Geom g = geom(gv);
+    const PhaseLayout pl = make_phase_layout(g, max_iters);
+    o[0] = plane_fast_geometry(g, pl); o[1] = plane_emission_geometry(g, pl);
+}
+
 static void plane_pass(const PlanePassPlan& P, long long* o) { o[0] = P.aligned; o[1] = P.grid_x; o[2] = P.grid_y; o[3] = P.block; }
 void hfp_plan_warp_generic(const int* gv, uint32_t out_off, long long* o) { plane_pass(plan_warp_generic(geom(gv), fake<void>(0x10000000u, out_off)), o); }
 void hfp_plan_copy(const int* gv, uint32_t src_off, uint32_t out_off, long long* o) {

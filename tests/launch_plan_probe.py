@@ -82,6 +82,12 @@ class Probe:
         self.lib.hfp_phase_layout(self._g(g), max_iters, o)
         return PhaseLayout(*o)
 
+    def plane_fast_geometry(self, g, max_iters):
+        """(plane_fast_geometry, plane_emission_geometry) of the geometry with the layout make_phase_layout gives it."""
+        o = (ctypes.c_longlong * 2)()
+        self.lib.hfp_plane_fast_geometry(self._g(g), max_iters, o)
+        return bool(o[0]), bool(o[1])
+
     def plan_warp_generic(self, g, out_off):
         o = (ctypes.c_longlong * 4)()
         self.lib.hfp_plan_warp_generic(self._g(g), out_off, o)

@@ -5,9 +5,12 @@ behind the warps that left them on their warp streams; a batch's update is one r
 blocking context fed the same frames with updateFrame, bit for bit: the three phase planes with their `complete` flags after every update,
 the newest blurred flow and m_totalFrameDelta after every chain.
 
-180 x 320 SDR and 360 x 640 HDR (the shapes of tests/test_chain_host_path_gpu.py: the fast plane kernel), 180 x 322 SDR, whose grid width
-is no multiple of 4 (the generic plane kernel; its planar frames take the element-by-element re-layout), and for the deferred planes
-2160 x 3840 HDR in a batch of 4, the smallest shape of tests/test_deferred_planes_gpu.py that defers.  (This file sorts behind
+180 x 320 SDR and 360 x 640 HDR (the shapes of tests/test_chain_host_path_gpu.py), 180 x 322 SDR, whose grid width is no multiple of 4 (its
+planar frames take the element-by-element re-layout), and for the deferred planes 2160 x 3840 HDR in a batch of 4, the smallest shape of
+tests/test_deferred_planes_gpu.py that defers.  Of these only 360 x 640 HDR takes the fast plane kernel (rs 1, lw 320, mx 296); 180 x 320
+SDR runs at rs 0 with a margin of mx = 588 > lw = 320 columns, beyond the single reflection, so the generic kernel builds its planes as it
+does those of 180 x 322 (tests/plane_builder_model.py builder, which tests/test_plane_builders_model.py holds to the compiled decision).
+This file compares twins; the fast kernel on 8-bit frames is held to the layout model by tests/test_plane_builders_gpu.py.  (This file sorts behind
 tests/test_timeline_gpu.py, which has to stay the first of the suite to switch a timeline on: see tests/test_chain_host_path_gpu.py.)"""
 import numpy as np
 import pytest
@@ -144,7 +147,7 @@ def test_every_entry_point_reaches_the_same_planes(native_lib, case, entry, plan
         members = [make(case, (capi.HF_FLAG_ASYNC if entry == "async" else 0) | (capi.HF_FLAG_PLANAR_IN if planar else 0))]
     c = members[0]
     rs = c.m_opticalFlowResScalar
-    assert ((case[2] >> rs) & 3 != 0) == (case == GENERIC)      # what hf_flow.hip launch_prep_fast declines: the generic plane kernel
+    assert ((case[2] >> rs) & 3 != 0) == (case == GENERIC)      # one of the things hf_flow.hip launch_prep_fast declines (see above)
     host = frames(case, seeds[0])[0 if planar else 1]
     if entry == "async":
         for f in host:
