@@ -215,6 +215,16 @@ class OpticalFlowCalc:
         args = self._pair_args("frameErrorMapEnqueue", a_ptrs, b_ptrs, stride_a, stride_b, planar)
         capi.check(self._lib.hf_frame_error_map_enqueue(self._ctx, *args, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
 
+    # ---- warp disagreement maps on the device (hf_warp_disagreement_map_enqueue) ----
+    def warpDisagreementMapEnqueue(self, ts, tile, maps_ptr):
+        """hf_warp_disagreement_map_enqueue: for every blending scalar of ts, per tile, how far the two warped halves of an output are
+        apart (what warpFrames(t, 0) and warpFrames(t, 1) would write, compared like frameErrorMapEnqueue) into map k of the device buffer
+        at maps_ptr (len(ts) maps of frameErrorMapShape(tile)[2] bytes, 16-byte aligned), behind everything this context has enqueued; one
+        launch, no frame written, only enqueues.  Download the buffer after sync() and view it with frame_error_maps()."""
+        n = len(ts)
+        t = (C.c_float * max(n, 1))(*[float(x) for x in ts])
+        capi.check(self._lib.hf_warp_disagreement_map_enqueue(self._ctx, n, t, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
+
     # ---- windowed SSIM on the device (hf_frame_ssim*) ----
     @staticmethod
     def _frame_ssim_dict(e):

@@ -30,6 +30,7 @@ HF_MAX_ERROR_PAIRS = 192          # frame pairs of one hf_frame_error_enqueue la
 HF_ERROR_SLOTS = 256              # result slots of a context
 HF_SSIM_SLOTS = 256               # result slots of hf_frame_ssim_enqueue, a range of their own
 HF_ERROR_MAP_TILES = (16, 32, 64)  # tile edges of hf_frame_error_map_enqueue, luma pixels
+HF_MAX_DISAGREEMENT_OUTPUTS = 24  # blending scalars of one hf_warp_disagreement_map_enqueue launch
 
 (HF_OK, HF_ERR_INVALID_ARGUMENT, HF_ERR_NO_DEVICE, HF_ERR_OUT_OF_MEMORY, HF_ERR_HIP, HF_ERR_STATE) = (0, -1, -2, -3, -4, -5)
 
@@ -193,6 +194,7 @@ SIGNATURES = {
     "hf_frame_error": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(HfFrameError)]),
     "hf_frame_error_map_shape": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)]),
     "hf_frame_error_map_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
+    "hf_warp_disagreement_map_enqueue": (_i, [_vp, _i, C.POINTER(C.c_float), _i, _vp]),
     "hf_frame_ssim_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "hf_frame_ssim_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameSsim)]),
     "hf_frame_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(HfFrameSsim)]),

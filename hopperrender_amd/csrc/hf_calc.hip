@@ -616,6 +616,27 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
     return HF_OK;
 }
 
+// What hf_warp_frames would read at this moment -- frames N-2 / N-1 and the previous flow -- and where its modes 0 and 1 would disagree,
+// per tile; ordered like hf_frame_error_enqueue.  Nothing of the context moves: no output, no warp bookkeeping, no span, no counters.
+int hf_warp_disagreement_map_enqueue(hf_ctx* c, int n_t, const float* t, int tile, void* device_maps) {
+    static_assert(HF_MAX_DISAGREEMENT_OUTPUTS == hf::kMaxDisagreementOutputs, "hopperflow.h");
+    const char* who = "hf_warp_disagreement_map_enqueue";
+    HF_CHECK_CTX(c);
+    if (!t) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null blending scalars", who);
+    if (n_t < 1 || n_t > HF_MAX_DISAGREEMENT_OUTPUTS) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: %d outputs, one launch takes 1 .. %d", who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS);
+    if (int rc = check_period_args(c, who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS, t, 0)) return rc;
+    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
+    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    hf::WarpPeriod p;
+    fill_period(c, 0, nullptr, nullptr, p);
+    if (!hf::launch_warp_disagreement(c->g, p.frame12, p.frame21, p.flow, p.flow_xy, n_t, t, tile, device_maps, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: nothing launched", who);
+    HF_HIP(c, hipGetLastError());
+    return note_launch(c, c->stream);   // a reader of the ring like the warps: the next asynchronous upload into frame N-2's slot waits for it
+}
+
 int hf_copy_frame(hf_ctx* c) {
     HF_CHECK_CTX(c);
     if (int rc = set_device(c)) return rc;

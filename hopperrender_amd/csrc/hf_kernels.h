@@ -173,6 +173,13 @@ bool launch_warp_periods(const Geom& g, int n, const WarpPeriod* periods, int mo
 void launch_warp(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
                  void* out, float t, int mode, float black, float white, hipStream_t stream,
                  hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);  // events: timestamps of the dispatch itself
+// Warp disagreement maps (hf_kernels.hip; hf_warp_disagreement_map_enqueue): for each of n_t <= kMaxDisagreementOutputs blending scalars,
+// per tile of the error maps' grid, sse / sad / max of |a - b| with a / b what output modes 0 / 1 of launch_warp would store at an element.
+// One launch, no frame written; maps = n_t maps of hf_error_tile [3][th][tw], 16-byte aligned, every entry of which the launch stores.
+// false: nothing launched (n_t or tile out of range).
+constexpr int kMaxDisagreementOutputs = 24;
+bool launch_warp_disagreement(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
+                              int n_t, const float* t, int tile, void* maps, hipStream_t stream);
 // copyFrameKernel, both planes in one launch.
 void launch_copy(const Geom& g, const void* src, void* out, float black, float white, hipStream_t stream);
 // Planar 4:2:0 frames at the device boundary (hf_planar.hip; HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT): planar (Y, U, V planes) <-> the

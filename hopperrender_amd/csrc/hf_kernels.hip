@@ -405,9 +405,9 @@ __device__ __forceinline__ unsigned warp_element(const Geom& g, const WarpArgs& 
     const int x21 = mirror_warp(ax - (int)roundf((float)ox21 * a.s21), W);
     const int y21 = mirror_warp(ay - (int)roundf((float)oy21 * a.s21 * hy), dim_y);
     const int par = cz ? (cx & 1) : 0;
+    HF_DBG_CHECK(x12 >= 0 && x21 >= 0 && y12 >= 0 && y21 >= 0 && y12 < dim_y && y21 < dim_y && (cz ? (x12 & ~1) + 1 : x12) < W && (cz ? (x21 & ~1) + 1 : x21) < W, 202);
     if (mode == 0) return A[plane + (size_t)y12 * Si + (cz ? (x12 & ~1) : x12) + par];
     if (mode == 1) return B[plane + (size_t)y21 * Si + (cz ? (x21 & ~1) : x21) + par];
-    HF_DBG_CHECK(x12 >= 0 && x21 >= 0 && y12 >= 0 && y21 >= 0 && y12 < dim_y && y21 < dim_y && (cz ? (x12 & ~1) + 1 : x12) < W && (cz ? (x21 & ~1) + 1 : x21) < W, 202);
     const float fa = (float)A[plane + (size_t)y12 * Si + (cz ? (x12 & ~1) : x12) + par];
     const float fb = (float)B[plane + (size_t)y21 * Si + (cz ? (x21 & ~1) : x21) + par];
     unsigned blended = (unsigned)__builtin_fmaf(fa, a.s21, fb * a.s12) & 0xFFFFu;     // :176-177 as compiled on gfx950
@@ -672,8 +672,14 @@ __device__ __forceinline__ void warp_finish(const WarpSrc<E, GROUP, ROWS, (VB / 
                                                  [&](const int r, const E* v) { __builtin_nontemporal_store(*(const nt_vec*)v, (nt_vec*)(out + (size_t)r * So)); });
 }
 
-template <typename E, int GROUP, int ROWS, int MODE, int CZ, int VB, bool DW>
-__device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a, int cy0, int cx0, int ti0, int ti1) {
+// SINK (warp_disagreement_kernel, MODE 2): instead of blending and storing, every element's two raw samples -- what MODE 0 and MODE 1
+// would store there -- go to sink.add(element within the thread's row, a, b), and sink.flush(ti) ends output ti; nothing is written.
+// SINK::each: every element takes the path of the ragged right edge, through warp_element.
+struct WarpStore { static constexpr bool each = false; };
+template <typename E, int GROUP, int ROWS, int MODE, int CZ, int VB, bool DW, typename SINK = WarpStore>
+__device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a, int cy0, int cx0, int ti0, int ti1, SINK* sink = nullptr) {
+    constexpr bool kStore = std::is_same<SINK, WarpStore>::value;
+    static_assert(kStore || MODE == 2, "a sink takes both samples");
     using T = ElemTraits<E>;
     using SV = typename StoreVec<VB>::type;
     constexpr int VEC = VB / sizeof(E);
@@ -683,13 +689,24 @@ __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a,
     const int dim_y = CZ ? (H >> 1) : H;
     const int nrows = min(ROWS, dim_y - cy0);
     const Levels lv = make_levels(a.black, a.white);
-    if (cx0 + VEC > W) {  // ragged right edge
+    if (SINK::each || cx0 + VEC > W) {  // ragged right edge
         for (int ti = ti0; ti < ti1; ti++) {
             WarpArgs at = a;
             at.s12 = a.s12v[ti]; at.s21 = a.s21v[ti]; at.out = a.outv[ti];
-            E* __restrict__ o = (E*)at.out + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
-            for (int r = 0; r < nrows; r++)
-                for (int i = 0; i < VEC && cx0 + i < W; i++) o[(size_t)r * So + i] = (E)warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r);
+            if constexpr (kStore) {
+                E* __restrict__ o = (E*)at.out + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
+                for (int r = 0; r < nrows; r++)
+                    for (int i = 0; i < VEC && cx0 + i < W; i++) o[(size_t)r * So + i] = (E)warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r);
+            } else {
+                for (int r = 0; r < nrows; r++)
+                    for (int i = 0; i < VEC && cx0 + i < W; i++) {
+                        at.mode = 0;
+                        const unsigned va = warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r);
+                        at.mode = 1;
+                        sink->add(i, va, warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r));
+                    }
+                sink->flush(ti);
+            }
         }
         return;
     }
@@ -880,8 +897,20 @@ __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a,
     }
   };
   auto finish = [&](const int ti, const Src& S) {
-    E* __restrict__ out = (E*)a.outv[ti] + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
-    warp_finish<E, GROUP, ROWS, MODE, CZ, VB>(S, a.s12v[ti], a.s21v[ti], out, So, nrows, lv);
+    if constexpr (kStore) {
+        E* __restrict__ out = (E*)a.outv[ti] + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
+        warp_finish<E, GROUP, ROWS, MODE, CZ, VB>(S, a.s12v[ti], a.s21v[ti], out, So, nrows, lv);
+    } else {
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) {
+            if (r >= nrows) continue;
+#pragma unroll
+            for (int k = 0; k < NG; k++)
+#pragma unroll
+                for (int i = 0; i < GROUP; i++) sink->add(k * GROUP + i, S.ra[r][k].v[i], S.rb[r][k].v[i]);
+        }
+        sink->flush(ti);
+    }
   };
   // (software pipelining -- requesting the runs of output ti + 1, of two outputs ahead, or of all outputs before blending
   //  output ti -- measured no faster since the dword-aligned loads: 49.9 / 52.8 / 53.8 us against 48.7 us for the plain
@@ -945,6 +974,120 @@ __global__ __launch_bounds__(64 * warp_max_waves(sizeof(E), GROUP, VB)) void war
     } else {
         const int rg = trow * kWarpTY + (lane / kWarpTX);
         if (rg < y_groups) warp_fast_body<E, GROUP, ROWS, MODE, 0, VB, DW>(g, a, rg * ROWS, cx0, ti0, ti1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Warp disagreement maps (hf_warp_disagreement_map_enqueue; the definition is in include/hopperflow.h)
+// ------------------------------------------------------------------------------------------
+// Per output t and per tile of the error maps' grid: sse, sad and max of |a - b|, a / b = what MODE 0 / MODE 1 of the warp would store at
+// an element.  No frame is written: the samples go from warp_fast_body (its flow lookups, displacement arithmetic, run loaders and
+// mirror-zone fallbacks, as they are) into a DisagreeSink instead of the blend.
+//
+// The mapping.  A workgroup owns a STRIP of one band of tile rows: `strip_tiles` tiles across (256 luma pixels at tile 16 and 32, 128 at
+// tile 64) by `tile` luma rows and the tile / 2 interleaved chroma rows under them; blockIdx.y is the band, blockIdx.x the strip.  A work
+// item is what a thread of the fast warp handles -- VB bytes of a row by 2 rows that share one flow-cell row -- so an item lies in ONE tile
+// (VB bytes are at most 16 elements, tiles start at multiples of 16) and, in a chroma row, holds U at even and V at odd elements of it.
+// Items are dealt to the lanes along the rows (neighbouring lanes: neighbouring runs), luma items first; both counts are multiples of 64,
+// so a wave is all luma or all chroma.  Per item and output the lane sums its differences in registers and adds them to the tile's
+// accumulator in LDS (ds_add_u64 / ds_add_u32 / ds_max_u32; an item without a difference adds nothing).  The outputs go in CHUNKS of
+// kMaxWarpOutputs -- the WarpArgs of a fused period, one per chunk in the kernel arguments; 24 outputs: four trips -- and behind each chunk
+// the workgroup stores its tiles of those outputs, one 16-byte store each, zeros included, and clears the accumulators.  Every entry of
+// every map belongs to one workgroup and one chunk: no global atomics, no memset.  Integer sums: the order of the additions cannot matter.
+// EACH: every element through warp_element (rs = 0, odd strides, frames too narrow for a run, t below 0): the same integers.
+constexpr int kDisBlock = 256;
+constexpr int kDisStripTiles = 16;
+constexpr int kDisChunks = kMaxDisagreementOutputs / kMaxWarpOutputs;
+static_assert(kDisChunks * kMaxWarpOutputs == kMaxDisagreementOutputs, "whole chunks");
+
+struct alignas(16) DisTile {   // the layout of hf_error_tile
+    unsigned long long sse;
+    uint32_t sad, mx;
+};
+struct DisagreeArgs {
+    int n_chunks;
+    int tile, lg;                    // tile edge in luma pixels = 1 << lg
+    int tw, th;
+    int strip_tiles;                 // tiles across of a strip (a power of two, at most kDisStripTiles)
+    size_t entries;                  // n_t 3 th tw (debug-bounds)
+    uint4* maps;                     // hf_error_tile [n_t][3][th][tw]
+    WarpArgs chunk[kDisChunks];      // outputs [c kMaxWarpOutputs, ...) as the n_out outputs of a period: s12v, s21v
+};
+static_assert(sizeof(Geom) + sizeof(DisagreeArgs) <= 4096, "kernel arguments: 4 KB");
+
+template <typename E, int CZ, bool EACH>
+struct DisagreeSink {
+    static constexpr bool each = EACH;
+    using Sq = typename std::conditional<sizeof(E) == 1, uint32_t, unsigned long long>::type;   // 32 8-bit squares fit 32 bits, two 16-bit ones do not
+    DisTile (*acc)[3][kDisStripTiles];
+    int txl;                         // the item's tile within the strip
+    Sq sse[2] = {0, 0};              // CZ: [0] U, [1] V
+    uint32_t sad[2] = {0, 0}, mx[2] = {0, 0};
+    __device__ __forceinline__ void add(int i, unsigned a, unsigned b) {
+        const uint32_t d = absdiff(a, b);
+        if (CZ && (i & 1)) { sse[1] += (Sq)d * d; sad[1] += d; mx[1] = d > mx[1] ? d : mx[1]; }
+        else               { sse[0] += (Sq)d * d; sad[0] += d; mx[0] = d > mx[0] ? d : mx[0]; }
+    }
+    __device__ __forceinline__ void flush(int ti) {
+#pragma unroll
+        for (int p = 0; p <= CZ; p++) {
+            if (sad[p]) {
+                HF_DBG_CHECK(ti >= 0 && ti < kMaxWarpOutputs && txl >= 0 && txl < kDisStripTiles, 281);
+                DisTile& t = acc[ti][CZ + p][txl];
+                atomicAdd(&t.sse, (unsigned long long)sse[p]); atomicAdd(&t.sad, sad[p]); atomicMax(&t.mx, mx[p]);
+            }
+            sse[p] = 0; sad[p] = 0; mx[p] = 0;
+        }
+    }
+};
+
+template <typename E, int GROUP, int VB, bool DW, bool EACH>
+__global__ __launch_bounds__(kDisBlock) void warp_disagreement_kernel(const Geom g, const DisagreeArgs d) {
+    constexpr int VEC = VB / sizeof(E);
+    __shared__ DisTile acc[kMaxWarpOutputs][3][kDisStripTiles];
+    const int band = blockIdx.y, strip = blockIdx.x, tile = d.tile;
+    const int x0 = (strip * d.strip_tiles) << d.lg;               // the strip's first luma column = first element of its interleaved chroma rows
+    const int ipr = (d.strip_tiles << d.lg) / VEC;                // items of a strip row, a power of two
+    const int lg_ipr = 31 - __builtin_clz(ipr);
+    const int n_y = ipr * (tile >> 1), n_c = ipr * (tile >> 2);   // items of the band's luma / chroma rows, two rows each
+    constexpr int kAcc = kMaxWarpOutputs * 3 * kDisStripTiles;
+    for (int e = threadIdx.x; e < kAcc; e += kDisBlock) (&acc[0][0][0])[e] = DisTile{0ull, 0u, 0u};
+    __syncthreads();
+    for (int c = 0; c < d.n_chunks; c++) {
+        const WarpArgs& a = d.chunk[c];
+        for (int it = threadIdx.x; it < n_y + n_c; it += kDisBlock) {
+            const bool cz = it >= n_y;
+            const int l = cz ? it - n_y : it;
+            const int cx0 = x0 + (l & (ipr - 1)) * VEC;
+            const int cy0 = band * (cz ? tile >> 1 : tile) + (l >> lg_ipr) * 2;
+            if (cx0 >= g.W || cy0 >= (cz ? g.H >> 1 : g.H)) continue;
+            const int txl = (cx0 - x0) >> d.lg;
+            // (the gathers themselves are warp_fast_body's and warp_element's, with their sites 201 .. 209; this is what they are handed)
+            HF_DBG_CHECK(cx0 >= 0 && cy0 >= 0 && cx0 % VEC == 0 && !(cy0 & 1) && txl < d.strip_tiles && ((cx0 + VEC - 1) >> d.lg) == (cx0 >> d.lg), 282);
+            if (cz) {
+                DisagreeSink<E, 1, EACH> sink{acc, txl};
+                warp_fast_body<E, GROUP, 2, 2, 1, VB, DW>(g, a, cy0, cx0, 0, a.n_out, &sink);
+            } else {
+                DisagreeSink<E, 0, EACH> sink{acc, txl};
+                warp_fast_body<E, GROUP, 2, 2, 0, VB, DW>(g, a, cy0, cx0, 0, a.n_out, &sink);
+            }
+        }
+        __syncthreads();
+        // the strip's tiles of this chunk's outputs: stored once, cleared for the next chunk
+        const int n_e = a.n_out * 3 * d.strip_tiles;
+        for (int e = threadIdx.x; e < n_e; e += kDisBlock) {
+            const int txl = e & (d.strip_tiles - 1), q = e / d.strip_tiles, tl = q / 3, pl = q - tl * 3;
+            const int tx = strip * d.strip_tiles + txl;
+            HF_DBG_CHECK(tl < kMaxWarpOutputs && txl < kDisStripTiles, 281);
+            const DisTile v = acc[tl][pl][txl];
+            acc[tl][pl][txl] = DisTile{0ull, 0u, 0u};
+            if (tx < d.tw) {
+                const size_t at = (((size_t)(c * kMaxWarpOutputs + tl) * 3u + (size_t)pl) * (size_t)d.th + (size_t)band) * (size_t)d.tw + (size_t)tx;
+                HF_DBG_CHECK(at < d.entries && band < d.th, 280);
+                d.maps[at] = uint4{(uint32_t)v.sse, (uint32_t)(v.sse >> 32), v.sad, v.mx};
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -1504,6 +1647,57 @@ bool launch_warp_periods(const Geom& g, int n, const WarpPeriod* periods, int mo
         else dispatch_warp<uint8_t>(g, L, b, mode, stream, e0, e1, pl);
     }
     return P.n_launches > 0;
+}
+
+// The run kernel of a shape, or EACH.  The rules are those of warp_fast_shape (hf_launch_plan.h) without its output side: 16 bytes per
+// thread and row where a thread then holds at most four flow cells, 8 bytes for 8-bit frames at rs = 1.
+template <typename E>
+static void dispatch_warp_disagreement(const Geom& g, const DisagreeArgs& d, bool runs, bool dw, hipStream_t stream) {
+    constexpr int V16 = 16 / (int)sizeof(E);
+    const dim3 grd((d.tw + d.strip_tiles - 1) / d.strip_tiles, d.th), blk(kDisBlock);
+#define HF_DIS(G, VB, D, EACH) HF_LAUNCH("warp_disagreement", (warp_disagreement_kernel<E, G, VB, D, EACH>), grd, blk, 0, stream, g, d)
+#define HF_DIS_DW(G, VB) do { if (dw) HF_DIS(G, VB, true, false); else HF_DIS(G, VB, false, false); } while (0)
+    const int g16 = warp_group(g, 16);
+    const bool ok = runs && (g.in_stride % 2) == 0 && g16 >= 2;
+    if (ok && g.W >= 2 * V16 && g16 == V16) HF_DIS_DW(V16, 16);
+    else if (ok && g.W >= 2 * V16 && g16 == V16 / 2) HF_DIS_DW(V16 / 2, 16);
+    else if (ok && g.W >= 2 * V16 && g16 == V16 / 4) HF_DIS_DW(V16 / 4, 16);
+    else if (ok && sizeof(E) == 1 && g.W >= 16 && g16 == 2) HF_DIS_DW(2, 8);
+    else HF_DIS(2, 16, false, true);
+#undef HF_DIS_DW
+#undef HF_DIS
+}
+
+bool launch_warp_disagreement(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
+                              int n_t, const float* t, int tile, void* maps, hipStream_t stream) {
+    if (n_t < 1 || n_t > kMaxDisagreementOutputs || (tile != 16 && tile != 32 && tile != 64)) return false;
+    DisagreeArgs d{};
+    d.n_chunks = (n_t + kMaxWarpOutputs - 1) / kMaxWarpOutputs;
+    d.tile = tile; d.lg = tile == 16 ? 4 : tile == 32 ? 5 : 6;
+    d.tw = (g.W + tile - 1) / tile; d.th = (g.H + tile - 1) / tile;
+    d.strip_tiles = tile == 64 ? 2 : 256 / tile;
+    d.entries = (size_t)n_t * 3u * (size_t)d.th * (size_t)d.tw;
+    d.maps = static_cast<uint4*>(maps);
+    bool runs = flow_xy != nullptr;
+    for (int c = 0; c < d.n_chunks; c++) {
+        WarpArgs& a = d.chunk[c];
+        a.frame12 = frame12; a.frame21 = frame21; a.flow = flow; a.flow_xy = flow_xy;
+        a.mode = 2; a.black = 0.0f; a.white = 255.0f;   // (no levels are applied: make_levels alone sees them)
+        a.n_out = n_t - c * kMaxWarpOutputs < kMaxWarpOutputs ? n_t - c * kMaxWarpOutputs : kMaxWarpOutputs;
+        for (int i = 0; i < a.n_out; i++) {
+            const float ti = t[c * kMaxWarpOutputs + i];
+            a.s12v[i] = ti; a.s21v[i] = 1.0f - ti;
+            runs = runs && ti >= 0.0f && ti <= 1.0f;
+        }
+        a.s12 = a.s12v[0]; a.s21 = a.s21v[0];
+    }
+    // dword-aligned source loads (load_run_dw): dword-aligned frames and rows that end on a dword, as in warp_fast_shape
+    const size_t esz = elem_size(g);
+    const bool dw = ((size_t)g.in_stride * esz) % 4 == 0 && ((size_t)g.W * esz) % 4 == 0 && ((size_t)g.H * g.in_stride * esz) % 4 == 0 &&
+                    (((uintptr_t)frame12 | (uintptr_t)frame21) & 3) == 0;
+    if (g.hdr) dispatch_warp_disagreement<uint16_t>(g, d, runs, dw, stream);
+    else dispatch_warp_disagreement<uint8_t>(g, d, runs, dw, stream);
+    return true;
 }
 
 template <typename E>

@@ -1,7 +1,8 @@
 """Leave-one-out interpolation quality of a clip, measured on the device.
 
     python -m hopperrender_amd.quality clip.y4m [--radius 16] [--sweep radius=5,16 --sweep blur=4,32] [--ssim] [--map 16] [--ssim-map 16] [--map-dir DIR]
-                                       [--report out.json]
+                                       [--disagreement 16] [--report out.json]
+    python -m hopperrender_amd.quality clip.y4m --confidence --target-fps 59.94 [--disagreement 16] [--report out.json]
     python -m hopperrender_amd.quality clip.nv12 --width 1920 --height 1080 [--hdr | --pix-fmt yuv420p10le] ...
 
 Every second frame of the clip is withheld: the sources S_j = frames[2 j] go through one asynchronous context exactly as a filter would
@@ -55,6 +56,28 @@ max_loss_q32, count}, with "sse" of the same tile beside them where --map runs a
 pair, plane Y, x, y and mean SSIM of the clip's worst luma tile.  With --map-dir one more PGM per evaluated pair (ssim_pair0001.pgm ...):
 the Y plane, one pixel per tile, round(255 min(1, sum_loss_q32 / count / 2^32)), 0 where count is 0 -- an absolute scale, so maps of
 different pairs and clips compare.  Without --ssim-map none of this is called, allocated or reported.
+
+--disagreement TILE / evaluate(disagreement=TILE) puts the one judge that needs no truth beside the ones that do: an output is blended
+from two warped halves, frame N-2 pushed forward by t and frame N-1 pulled back by 1 - t, and where the flow is wrong the two differ.
+Straight behind each evaluated pair's period, before the next period moves the ring, the disagreement map at t = 0.5
+(hf_warp_disagreement_map_enqueue: sse, sad, max_abs of the two halves' difference per tile and plane, one launch, no frame written) goes
+into a device buffer of its own per chunk, read once per chunk.  Each pair's "interpolated" dict gains "disagreement": the shape of
+"map" -- tile, shape, and per plane "worst" and "share_top1pct" -- and per plane the totals sse, sad, max_abs; where --map runs at the
+same tile size each plane also carries "overlap_top1pct": with k = ceil(tiles / 100), how many of the k worst tiles of the error map
+are among the k worst of the disagreement map (both in the order of "worst"), over k -- how well disagreement predicts where the real
+error is; None where either plane's sse is 0.  clip["disagreement"][plane] holds the summed sse and the hits summed over the k's summed
+of the pairs where that is defined, clip["worst_tile_disagreement"] is worst_tile's twin, and --map-dir gains dis_pair0001.pgm ... by
+the rule of the error maps' PGMs, scaled to their own clip maximum.  Without the option none of this is called, allocated or reported.
+
+--confidence --target-fps F / confidence() is that judge ON ITS OWN, on every frame of the clip at the real output schedule: nothing is
+withheld, frame j is the source of period j, the t's of a period are those of protocol.BlendSchedule(source, target).plan, the period is
+submitted with no outputs (update and flow only) and the disagreement maps of its t's are enqueued behind it -- no output frame exists
+in this mode.  Gating as above: nothing before a flow exists, the pair shown before any flow is listed as warm-up, the last frame is
+submitted once more.  The report has per period the pair, the t's and per t and plane sse, sad, max_abs, rms = sqrt(sse / count) and
+the worst tile; per clip the plane totals, the worst (period, t) by the rms of Y and the per-period mean rms of Y as a list.  The maps
+are read once per chunk, a chunk being the periods whose maps fit CONFIDENCE_MAP_BYTES and whose sources fit CONFIDENCE_SOURCE_BYTES.
+On the command line --confidence takes the flow settings, --disagreement TILE and --sweep; the options of the leave-one-out run
+(--ssim, --map, --ssim-map, --map-dir, --detect-cuts, --black, --white) are refused beside it.
 """
 import argparse
 import itertools
@@ -68,6 +91,9 @@ SUMS = ("sse", "sad", "max_abs", "n_differ", "count")
 SSIM_SUMS = ("sum_loss_q32", "max_loss_q32", "count")
 SETTINGS = {"search_radius": 16, "delta_scalar": 8, "neighbor_scalar": 6, "blur_radius": 0, "iterations": 0, "max_calc_res": 270}
 PAIRS_PER_READ = 128   # two result slots per pair (interpolation, repeat) out of HF_ERROR_SLOTS
+CONFIDENCE_MAP_BYTES = 32 << 20   # confidence(): device bytes of disagreement maps between two reads (2160p at tile 16: 10 periods of 2 or 3 outputs)
+CONFIDENCE_SOURCE_BYTES = 512 << 20   # ... and device bytes of a chunk's sources, which are all uploaded before it is submitted (2160p HDR: 21 periods)
+MAX_DISAGREEMENT_OUTPUTS = 24    # blending scalars of one hf_warp_disagreement_map_enqueue launch
 
 
 def psnr(sse, count, peak):
@@ -171,7 +197,37 @@ def _map_dict(m, tile):
                 **{p: {"worst": _worst_tiles(m[i], tile), "share_top1pct": _share_top1pct(m[i])} for i, p in enumerate(PLANES)})
 
 
-def _write_map_pgms(map_dir, luma, tile, H, W):
+def _top1pct(m, tile):
+    """the ceil(tiles / 100) worst tiles of one plane's map, in the order of _worst_tiles, as (y, x) in tiles"""
+    return [(t["y"] // tile, t["x"] // tile) for t in _worst_tiles(m, tile, (m.size + 99) // 100)]
+
+
+def _overlap_top1pct(err, dis, tile):
+    """(hits, k): how many of the k = ceil(tiles / 100) worst tiles of the error map's plane are among the k worst of the disagreement
+    map's; None where either plane's sse is 0"""
+    if not int(err["sse"].astype(object).sum()) or not int(dis["sse"].astype(object).sum()):
+        return None
+    a, b = _top1pct(err, tile), _top1pct(dis, tile)
+    return len(set(a) & set(b)), len(a)
+
+
+def _plane_totals(m):
+    """sse, sad, max_abs of one plane's map as plain ints"""
+    return {"sse": int(m["sse"].astype(object).sum()), "sad": int(m["sad"].astype(object).sum()), "max_abs": int(m["max_abs"].max())}
+
+
+def _disagreement_dict(m, tile, overlap=None):
+    """one pair's disagreement map [3][th][tw] as the report's "disagreement" entry; overlap: per plane _overlap_top1pct against the
+    pair's error map at the same tile, or None where there is no such map"""
+    out = _map_dict(m, tile)
+    for i, p in enumerate(PLANES):
+        out[p].update(_plane_totals(m[i]))
+        if overlap is not None:
+            out[p]["overlap_top1pct"] = None if overlap[i] is None else overlap[i][0] / overlap[i][1]
+    return out
+
+
+def _write_map_pgms(map_dir, luma, tile, H, W, prefix="map"):
     """luma: [(pair, Y map [th][tw])] -> one binary PGM per pair, sqrt(sse / count) per tile scaled to the largest value of the clip"""
     import numpy as np
     os.makedirs(map_dir, exist_ok=True)
@@ -181,7 +237,7 @@ def _write_map_pgms(map_dir, luma, tile, H, W):
     rms = [np.sqrt(m["sse"].astype(np.float64) / np.outer(rows, cols)) for _, m in luma]
     top = max(float(r.max()) for r in rms)
     for (pair, _), r in zip(luma, rms):
-        with open(os.path.join(map_dir, f"map_pair{pair:04d}.pgm"), "wb") as f:
+        with open(os.path.join(map_dir, f"{prefix}_pair{pair:04d}.pgm"), "wb") as f:
             f.write(b"P5\n%d %d\n255\n" % (tw, th))
             f.write(np.rint(r * (255.0 / top) if top > 0 else r).astype(np.uint8).tobytes())
 
@@ -243,7 +299,7 @@ def _minus(a, b):
 
 
 def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
-             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, ssim_map=0, **settings):
+             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, ssim_map=0, disagreement=0, **settings):
     """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
     settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
     library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
@@ -251,14 +307,18 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
     ssim: also score every comparison with the device's windowed SSIM (module docstring); off, nothing of it is called or reported.
     error_map: 16, 32 or 64 -- also the per-tile error map of every interpolation (module docstring); 0, nothing of it is called or
     reported.  ssim_map: 16, 32 or 64 -- also the per-tile SSIM map of every interpolation (module docstring); 0, nothing of it is
-    called, allocated or reported.  map_dir: with error_map or ssim_map, a directory for one PGM heat map of the Y plane per evaluated
-    pair and map."""
+    called, allocated or reported.  disagreement: 16, 32 or 64 -- also the warp disagreement map of every evaluated pair at t = 0.5, the
+    judge that needs no truth, and beside error_map of the same tile how well it predicts the real error (module docstring); 0, nothing
+    of it is called, allocated or reported.  map_dir: with error_map, ssim_map or disagreement, a directory for one PGM heat map of the
+    Y plane per evaluated pair and map."""
     if error_map not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: error_map {error_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
     if ssim_map not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: ssim_map {ssim_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
-    if map_dir and not error_map and not ssim_map:
-        raise ValueError("evaluate: map_dir needs error_map or ssim_map")
+    if disagreement not in (0, 16, 32, 64):
+        raise ValueError(f"evaluate: disagreement {disagreement}, a tile of 16, 32 or 64 luma pixels (0: none)")
+    if map_dir and not error_map and not ssim_map and not disagreement:
+        raise ValueError("evaluate: map_dir needs error_map, ssim_map or disagreement")
     unknown = set(settings) - set(SETTINGS)
     if unknown:
         raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
@@ -281,6 +341,11 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         from .calc import frame_ssim_maps
         stiles_x, stiles_y, smap_bytes = main.frameSsimMapShape(ssim_map)
         smaps_buf = dev.buffer(smap_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
+    dis_buf, luma_dis, overlaps = None, [], []       # disagreement: the same again; overlaps: per pair and plane (hits, k) or None
+    if disagreement:
+        from .calc import frame_error_maps
+        dtiles_x, dtiles_y, dmap_bytes = main.frameErrorMapShape(disagreement)
+        dis_buf = dev.buffer(dmap_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
     take = lambda pool, nbytes: pool.pop() if pool else dev.buffer(nbytes)
     src = {}    # period -> device frame of its source; the last three outlive a chunk (the context's ring still references them)
     try:
@@ -324,6 +389,8 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                 truth, repeat, out = jobs.get(s["period"], (None, None, scratch))
                 main.interpolatePeriod(b.ptr, [0.5], [out.ptr], 2)
                 if s["evaluated"]:
+                    if disagreement:                # the frames and the flow this period's warp used: before the next period moves the ring
+                        main.warpDisagreementMapEnqueue([0.5], disagreement, dis_buf.ptr + (slot // 2) * dmap_bytes)
                     main.frameErrorEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
                     if ssim:
                         main.frameSsimEnqueue([out.ptr, repeat.ptr], [truth.ptr, truth.ptr], slot)
@@ -346,6 +413,9 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
             if ssim_map and slot:
                 import numpy as np
                 got_smaps = frame_ssim_maps(smaps_buf.download(np.uint8, (slot // 2) * smap_bytes), slot // 2, stiles_x, stiles_y)
+            if disagreement and slot:
+                import numpy as np
+                got_dis = frame_error_maps(dis_buf.download(np.uint8, (slot // 2) * dmap_bytes), slot // 2, dtiles_x, dtiles_y)
             for i, s in enumerate(s for s in chunk if s["evaluated"]):
                 row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
                        "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
@@ -363,6 +433,13 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     row["interpolated"]["ssim_map"] = _ssim_map_dict(got_smaps[i], ssim_map, got_maps[i] if error_map == ssim_map else None)
                     if map_dir:
                         luma_smaps.append((s["pair"], got_smaps[i][0].copy()))
+                if disagreement:
+                    over = [_overlap_top1pct(got_maps[i][k], got_dis[i][k], disagreement) for k in range(3)] if error_map == disagreement else None
+                    row["interpolated"]["disagreement"] = _disagreement_dict(got_dis[i], disagreement, over)
+                    if over is not None:
+                        overlaps.append(over)
+                    if map_dir:
+                        luma_dis.append((s["pair"], got_dis[i][0].copy()))
                 rows.append(row)
             # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
             last = chunk[-1]["period"]
@@ -373,7 +450,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         aux.close()
         if filt is not None:
             filt.close()
-        for b in free_in + free_out + list(src.values()) + [b for b in (maps_buf, smaps_buf) if b is not None]:
+        for b in free_in + free_out + list(src.values()) + [b for b in (maps_buf, smaps_buf, dis_buf) if b is not None]:
             b.free()
     worst = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["psnr"] is None else r["interpolated"]["Y"]["psnr"])
     clip = {"interpolated": _aggregate(rows, "interpolated", peak), "repeat": _aggregate(rows, "repeat", peak),
@@ -402,10 +479,129 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         clip["worst_tile_ssim"] = None if low is None else {"pair": low[0], "plane": "Y", "x": low[1]["x"], "y": low[1]["y"], "ssim": low[1]["ssim"]}
         if map_dir:
             _write_ssim_pgms(map_dir, luma_smaps)
+    if disagreement:
+        clip["disagreement"] = {}
+        for k, p in enumerate(PLANES):
+            clip["disagreement"][p] = {"sse": sum(r["interpolated"]["disagreement"][p]["sse"] for r in rows)}
+            if error_map == disagreement:
+                seen = [o[k] for o in overlaps if o[k] is not None]
+                clip["disagreement"][p]["overlap_top1pct"] = sum(h for h, _ in seen) / sum(n for _, n in seen) if seen else None
+        top = max(rows, key=lambda r: r["interpolated"]["disagreement"]["Y"]["worst"][0]["sse"])   # (the first of equals: the earlier pair)
+        t = top["interpolated"]["disagreement"]["Y"]["worst"][0]
+        clip["worst_tile_disagreement"] = {"pair": top["pair"], "plane": "Y", "x": t["x"], "y": t["y"], "sse": t["sse"]}
+        if map_dir:
+            _write_map_pgms(map_dir, luma_dis, disagreement, H, W, prefix="dis")
     return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
             "settings": dict(st, black_level=float(black), white_level=float(white)),
             "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
             "pairs": rows, "clip": clip, "scene_cuts": cuts if detect_scene_cuts else None}
+
+
+# ---- confidence without a truth frame: the disagreement of the two warped halves at the real output schedule ----
+def confidence_schedule(n_frames, source_frame_time, target_frame_time):
+    """The periods of a confidence run over n_frames frames, every frame a source: one dict per period, in order --
+         period        j
+         source_frame  index of the frame submitted (frames[j]; the last one once more at the end, so that the last pair is reached)
+         flow          a flow is calculated (the filter's gating: from the third frame on)
+         pair          the pair (frames[pair], frames[pair + 1]) the period's outputs would show, None before there is one
+         evaluated     False for pair 0, which is shown before any flow has been calculated (warm-up)
+         t             the blending scalars of the period's outputs: protocol.BlendSchedule(source, target).plan, period by period"""
+    from .protocol import BlendSchedule
+    if n_frames < 3:
+        raise ValueError(f"a confidence run needs at least 3 frames, got {n_frames}")
+    plan = BlendSchedule(source_frame_time, target_frame_time).plan(n_frames + 1)
+    out = []
+    for j in range(n_frames + 1):
+        pair = j - 2 if j >= 2 else None
+        out.append({"period": j, "source_frame": min(j, n_frames - 1), "flow": j >= 2, "pair": pair,
+                    "evaluated": pair is not None and pair >= 1, "t": [float(t) for t in plan[j]]})
+    return out
+
+
+def confidence(frames, hdr, H, W, *, source_frame_time, target_frame_time, tile=16, device_index=0, device=None, **settings):
+    """How far the two warped halves of every output of a clip are apart, at the real output schedule and with nothing withheld -> report
+    dict (module docstring).  frames: flat NV12 uint8 / P010 uint16 host frames of H x W, stride W; source_frame_time / target_frame_time
+    in 100 ns units, as the filter counts them; tile: 16, 32 or 64 luma pixels; settings: those of evaluate().  No output frame exists:
+    every period is submitted with no outputs and the maps of its t's are enqueued behind it."""
+    if tile not in (16, 32, 64):
+        raise ValueError(f"confidence: tile {tile}, 16, 32 or 64 luma pixels")
+    unknown = set(settings) - set(SETTINGS)
+    if unknown:
+        raise TypeError(f"confidence: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
+    import numpy as np
+    from .calc import frame_error_maps
+    st = dict(SETTINGS, **{k: int(v) for k, v in settings.items()})
+    dev = device or _Device(device_index)
+    sched = confidence_schedule(len(frames), source_frame_time, target_frame_time)
+    main = dev.calc(hdr, H, W, 0.0, 255.0, st)       # (no levels are applied to the two halves)
+    frame_bytes = int(main.input_frame_bytes)
+    tiles_x, tiles_y, map_bytes = main.frameErrorMapShape(tile)
+    # chunks by bytes: the periods whose maps fit CONFIDENCE_MAP_BYTES and whose sources -- all uploaded before the chunk is submitted --
+    # fit CONFIDENCE_SOURCE_BYTES, one period at the least
+    chunks, held, sources = [[]], 0, 0
+    for s in sched:
+        need = len(s["t"]) * map_bytes if s["evaluated"] else 0
+        if chunks[-1] and ((held and held + need > CONFIDENCE_MAP_BYTES) or sources + frame_bytes > CONFIDENCE_SOURCE_BYTES):
+            chunks.append([])
+            held = sources = 0
+        chunks[-1].append(s)
+        held += need
+        sources += frame_bytes
+    maps_buf = dev.buffer(max(sum(len(s["t"]) * map_bytes for s in chunk if s["evaluated"]) for chunk in chunks))
+    counts = {"Y": H * W, "U": (H // 2) * (W // 2), "V": (H // 2) * (W // 2)}
+    free_in, src, rows = [], {}, []
+    try:
+        for chunk in chunks:
+            for s in chunk:
+                src[s["period"]] = free_in.pop() if free_in else dev.buffer(frame_bytes)
+                src[s["period"]].upload(frames[s["source_frame"]])
+            used = 0
+            for s in chunk:
+                b = src[s["period"]]
+                if not s["flow"]:
+                    main.updateFrameDeviceRef(b.ptr)
+                    continue
+                main.interpolatePeriod(b.ptr, [], [], 2)        # update and flow only
+                if s["evaluated"]:
+                    for k in range(0, len(s["t"]), MAX_DISAGREEMENT_OUTPUTS):
+                        ts = s["t"][k:k + MAX_DISAGREEMENT_OUTPUTS]
+                        main.warpDisagreementMapEnqueue(ts, tile, maps_buf.ptr + used)
+                        used += len(ts) * map_bytes
+            main.sync()
+            got = frame_error_maps(maps_buf.download(np.uint8, used), used // map_bytes, tiles_x, tiles_y) if used else []
+            at = 0
+            for s in (s for s in chunk if s["evaluated"]):
+                outputs = []
+                for t in s["t"]:
+                    o = {"t": t}
+                    for i, p in enumerate(PLANES):
+                        o[p] = _plane_totals(got[at][i])
+                        o[p]["rms"] = math.sqrt(o[p]["sse"] / counts[p])
+                        o[p]["worst"] = _worst_tiles(got[at][i], tile, 1)[0]
+                    outputs.append(o)
+                    at += 1
+                rows.append({"period": s["period"], "pair": s["pair"], "source_frames": [s["pair"], s["pair"] + 1], "t": list(s["t"]),
+                             "outputs": outputs, "mean_rms_y": sum(o["Y"]["rms"] for o in outputs) / len(outputs)})
+            last = chunk[-1]["period"]                          # the ring still references the last three sources
+            free_in += [src.pop(j) for j in sorted(src) if j <= last - 3]
+    finally:
+        main.close()
+        for b in free_in + list(src.values()) + [maps_buf]:
+            b.free()
+    every = [(r, o) for r in rows for o in r["outputs"]]
+    clip = {}
+    for p in PLANES:
+        sse = sum(o[p]["sse"] for _, o in every)
+        clip[p] = {"sse": sse, "sad": sum(o[p]["sad"] for _, o in every), "max_abs": max(o[p]["max_abs"] for _, o in every),
+                   "rms": math.sqrt(sse / (counts[p] * len(every)))}
+    r, o = max(every, key=lambda ro: ro[1]["Y"]["sse"])         # (the first of equals: the earlier period, the earlier t)
+    clip["worst"] = {"period": r["period"], "pair": r["pair"], "t": o["t"], "rms_y": o["Y"]["rms"]}
+    clip["mean_rms_y"] = [r["mean_rms_y"] for r in rows]
+    return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "frames": len(frames)}, "settings": st,
+            "schedule": {"source_frame_time": int(source_frame_time), "target_frame_time": int(target_frame_time)},
+            "tile": tile, "shape": [int(tiles_y), int(tiles_x)],
+            "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
+            "periods": rows, "clip": clip}
 
 
 # ---- command line ----
@@ -477,8 +673,15 @@ def parse_args(argv=None):
     ap.add_argument("--ssim-map", type=int, default=0, choices=(0, 16, 32, 64), metavar="TILE",
                     help="also locate the structural loss: per-tile SSIM maps of every interpolation on the tile grid of --map; beside --map TILE of "
                          "the same size each worst tile carries its squared error too")
+    ap.add_argument("--disagreement", type=int, default=0, choices=(0, 16, 32, 64), metavar="TILE",
+                    help="also the judge that needs no truth: per-tile disagreement of the two warped halves of every evaluated pair at t = 0.5; beside "
+                         "--map TILE of the same size, how well it predicts where the real error is.  With --confidence: the tile (default 16)")
+    ap.add_argument("--confidence", action="store_true",
+                    help="no leave-one-out: every frame is a source, and the disagreement of the two warped halves is reported for every output of "
+                         "the real schedule (--target-fps); no output frame is made")
+    ap.add_argument("--target-fps", type=float, default=None, help="with --confidence: the output rate whose blending scalars are judged")
     ap.add_argument("--map-dir", default=None, metavar="DIR",
-                    help="with --map or --ssim-map: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
+                    help="with --map, --ssim-map or --disagreement: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
     ap.add_argument("--report", default=None, help="write the reports as JSON")
     a = ap.parse_args(argv)
     if a.pix_fmt is None:
@@ -487,8 +690,17 @@ def parse_args(argv=None):
         a.hdr = True
     elif a.hdr:
         ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
-    if a.map_dir and not a.map and not a.ssim_map:
-        ap.error("--map-dir needs --map TILE or --ssim-map TILE")
+    if a.map_dir and not a.map and not a.ssim_map and not a.disagreement:
+        ap.error("--map-dir needs --map TILE, --ssim-map TILE or --disagreement TILE")
+    if a.confidence and not (a.target_fps and a.target_fps > 0):
+        ap.error("--confidence needs --target-fps F")
+    if a.confidence:   # no truth, no output frame, no levels: what only the leave-one-out run can honour is refused, not ignored
+        given = [name for name, on in (("--ssim", a.ssim), ("--map", a.map), ("--ssim-map", a.ssim_map), ("--map-dir", a.map_dir),
+                                       ("--detect-cuts", a.detect_cuts), ("--black", a.black != 0.0), ("--white", a.white != 255.0)) if on]
+        if given:
+            ap.error(f"--confidence does not take {', '.join(given)}")
+    elif a.target_fps is not None:
+        ap.error("--target-fps needs --confidence")
     try:
         a.sweeps = parse_sweeps(a.sweep)
     except ValueError as e:
@@ -513,12 +725,21 @@ def main(argv=None, device=None):
     base = {"search_radius": a.radius, "delta_scalar": a.delta, "neighbor_scalar": a.neighbor, "blur_radius": a.blur,
             "iterations": a.iterations, "max_calc_res": a.max_calc_res}
     reports = []
-    for k, sweep in enumerate(a.sweeps):
+    for sweep in (a.sweeps if a.confidence else []):
+        st = dict(base, **sweep)
+        rep = confidence(frames, clip.hdr, clip.height, clip.width, source_frame_time=int(round(1e7 / clip.source_fps)),
+                         target_frame_time=int(round(1e7 / a.target_fps)), tile=a.disagreement or 16, device_index=a.device, device=device, **st)
+        reports.append(rep)
+        c = rep["clip"]
+        print(" ".join(f"{k}={st[k]}" for k in SETTINGS) + f"  periods {len(rep['periods'])}  outputs {sum(len(r['t']) for r in rep['periods'])}  "
+              f"disagreement rms Y/U/V {c['Y']['rms']:.3f} {c['U']['rms']:.3f} {c['V']['rms']:.3f}  worst period {c['worst']['period']} "
+              f"t {c['worst']['t']:.4f} ({c['worst']['rms_y']:.3f})")
+    for k, sweep in enumerate([] if a.confidence else a.sweeps):
         st = dict(base, **sweep)
         map_dir = a.map_dir and (os.path.join(a.map_dir, f"setting{k:02d}") if len(a.sweeps) > 1 else a.map_dir)
         rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
                        scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
-                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, ssim_map=a.ssim_map, **st)
+                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, ssim_map=a.ssim_map, disagreement=a.disagreement, **st)
         reports.append(rep)
         c = rep["clip"]
         knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
@@ -530,7 +751,10 @@ def main(argv=None, device=None):
                   f"worst pair {c['worst_pair_ssim']['pair']} ({_ss(c['worst_pair_ssim']['ssim_y'])})" if a.ssim else "") + (
                   f"  worst tile pair {c['worst_tile']['pair']} at ({c['worst_tile']['x']}, {c['worst_tile']['y']}) sse {c['worst_tile']['sse']}" if a.map else "") + (
                   f"  worst SSIM tile pair {c['worst_tile_ssim']['pair']} at ({c['worst_tile_ssim']['x']}, {c['worst_tile_ssim']['y']}) "
-                  f"{_ss(c['worst_tile_ssim']['ssim'])}" if a.ssim_map and c.get("worst_tile_ssim") else ""))
+                  f"{_ss(c['worst_tile_ssim']['ssim'])}" if a.ssim_map and c.get("worst_tile_ssim") else "") + (
+                  f"  worst disagreement pair {c['worst_tile_disagreement']['pair']} at ({c['worst_tile_disagreement']['x']}, "
+                  f"{c['worst_tile_disagreement']['y']})" + (f"  overlap Y {_ss(c['disagreement']['Y']['overlap_top1pct'])}" if a.map == a.disagreement else "")
+                  if a.disagreement else ""))
     if a.report:
         with open(a.report, "w") as f:
             json.dump({"input": a.input, "reports": reports}, f, indent=1)

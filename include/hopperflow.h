@@ -495,6 +495,36 @@ int hf_frame_ssim_map_shape(const hf_ctx* ctx, int tile, int* tiles_x, int* tile
 int hf_frame_ssim_map_enqueue(hf_ctx* ctx, int n, const void* const* device_a, const void* const* device_b, int stride_a, int stride_b,
                               int planar, int peak, int tile, void* device_maps);
 
+/* ---- Warp disagreement maps on the device: confidence WITHOUT a truth frame ----
+ * Every judge above needs a second frame to compare with, so a clip can only be judged leave-one-out.  A blended output, though, is made
+ * of two warped halves -- frame N-2 pushed forward by t and frame N-1 pulled back by 1 - t -- and where the flow is right the two show
+ * the same picture; where it is wrong (occlusion, a motion boundary, motion beyond the search reach) they differ.  This call measures
+ * that difference per tile of the error maps' grid, for up to HF_MAX_DISAGREEMENT_OUTPUTS blending scalars of one source period, in one
+ * launch and without writing a frame.  Step by step:
+ *   1. Sources.  What hf_warp_frames would read if it were called at the same moment: frames N-2 and N-1 of ctx's ring (always NV12 /
+ *      P010, whatever HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT say) and the previous blurred flow.  No state is checked that
+ *      hf_warp_frames does not check.
+ *   2. Per t[k] and per element (plane, row, column) of the picture:  a = the value hf_warp_frames(ctx, t[k], HF_MODE_WARPED_FRAME_12)
+ *      writes there,  b = the value hf_warp_frames(ctx, t[k], HF_MODE_WARPED_FRAME_21) writes there -- the raw gathered samples of the
+ *      two frames, no levels, no blend;  d = |a - b|.
+ *   3. Tiles, planes and sums are those of hf_frame_error_map_enqueue, steps 1 to 3: `tile` is 16, 32 or 64, tw and th come from
+ *      hf_frame_error_map_shape, the interleaved UV plane is split into U and V, and per tile  sse = sum d^2,  sad = sum d,
+ *      max_abs = max d.
+ *   4. device_maps is ONE caller-owned device buffer of n_t bytes_per_map bytes, 16-byte aligned, holding
+ *      `struct hf_error_tile [n_t][3][th][tw]`; the map of t[k] starts at byte k bytes_per_map.  EVERY entry is written by the launch,
+ *      zeros included.
+ *   5. The identity that defines it: map k is byte for byte what hf_frame_error_map_enqueue stores for the pair (mode-0 output at t[k],
+ *      mode-1 output at t[k]) of this context, with any output stride and planar = 0.
+ * The call only enqueues, ordered exactly like hf_frame_error_enqueue (behind every update, chain, warp and copy of ctx, the warp stream
+ * of an HF_FLAG_DUAL_STREAM context included; a batch member on its batch's stream).  Straight behind hf_interpolate_period or
+ * hf_batch_run_period* it describes the frames and the flow that period's warps used.  The frames of an hf_update_frame_device_ref
+ * update must stay as they are until the launch has run.  Nothing observable of ctx changes: not the output frame or its target, not
+ * m_warpCalcTime, no profile span, no diagnostic counter, no error or SSIM slot.  Read the maps with hf_memcpy_d2h after hf_sync.
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued: a NULL t, n_t outside [1, HF_MAX_DISAGREEMENT_OUTPUTS], any t[k] > 1 (hf_warp_frames'
+ * own rule), a tile outside {16, 32, 64}, a NULL or misaligned device_maps.  Additive to ABI version 6. */
+#define HF_MAX_DISAGREEMENT_OUTPUTS 24   /* = HF_MAX_PERIOD_OUTPUTS_WIDE */
+int hf_warp_disagreement_map_enqueue(hf_ctx* ctx, int n_t, const float* t, int tile, void* device_maps);
+
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
 /* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
