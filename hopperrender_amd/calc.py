@@ -225,6 +225,20 @@ class OpticalFlowCalc:
         t = (C.c_float * max(n, 1))(*[float(x) for x in ts])
         capi.check(self._lib.hf_warp_disagreement_map_enqueue(self._ctx, n, t, int(tile), C.c_void_p(maps_ptr or 0)), self._ctx)
 
+    # ---- guarded blend on the device (hf_guarded_blend_enqueue) ----
+    def guardedBlendEnqueue(self, ts, tile, lo_q4, hi_q4, maps_ptr, out_ptrs):
+        """hf_guarded_blend_enqueue: for every blending scalar of ts the blended frame of warpFrames(t, 2), faded into the plain cross-fade
+        of the two source frames where the warped halves disagree, into the device frame out_ptrs[k] (output_frame_bytes each, NV12 / P010
+        at the output stride); map k of the buffer at maps_ptr receives what warpDisagreementMapEnqueue(ts, tile, maps_ptr) stores.  A
+        tile's mean luma difference in sixteenths of an 8-bit code up to lo_q4 keeps the blend, from hi_q4 on it is all cross-fade;
+        (4080, 4081) is guard off.  Behind everything this context has enqueued; only enqueues.  guard_weights() shows the mask."""
+        n = len(ts)
+        if len(out_ptrs) != n:
+            raise ValueError(f"guardedBlendEnqueue: {n} blending scalars, {len(out_ptrs)} output frames")
+        t = (C.c_float * max(n, 1))(*[float(x) for x in ts])
+        outs = (C.c_void_p * max(n, 1))(*[C.c_void_p(p or 0) for p in out_ptrs])
+        capi.check(self._lib.hf_guarded_blend_enqueue(self._ctx, n, t, int(tile), int(lo_q4), int(hi_q4), C.c_void_p(maps_ptr or 0), outs), self._ctx)
+
     # ---- windowed SSIM on the device (hf_frame_ssim*) ----
     @staticmethod
     def _frame_ssim_dict(e):
@@ -380,6 +394,29 @@ def frame_error_maps(raw, n, tiles_x, tiles_y):
     if a.size < need:
         raise ValueError(f"frame_error_maps: {a.size} bytes, {n} maps of 3 x {tiles_y} x {tiles_x} tiles need {need}")
     return a[:need].view(ERROR_TILE_DTYPE).reshape(n, 3, tiles_y, tiles_x)
+
+
+def guard_weights(maps, tile, lo_q4, hi_q4, H, W, hdr):
+    """The mask of hf_guarded_blend_enqueue from downloaded disagreement maps (frame_error_maps(): [n][3][th][tw]), steps 3 and 4 of its
+    definition in include/hopperflow.h: (tile_weights [n][th][tw], luma_weights [n][H][W]), int64, 0 .. 256 -- 0 keeps the
+    motion-compensated blend, 256 is the cross-fade.  A chroma element (cx, cy) takes luma_weights[k][2 * cy][cx & ~1]."""
+    if tile not in (16, 32, 64) or not 0 <= lo_q4 < hi_q4 <= 65535:
+        raise ValueError(f"guard_weights: tile {tile} not 16, 32 or 64, or thresholds {lo_q4}, {hi_q4} outside 0 <= lo_q4 < hi_q4 <= 65535")
+    lg = tile.bit_length() - 1
+    th, tw = (H + tile - 1) // tile, (W + tile - 1) // tile
+    sad = np.asarray(maps["sad"])[:, 0].astype(np.int64)
+    if sad.shape[1:] != (th, tw):
+        raise ValueError(f"guard_weights: maps of {sad.shape[1:]} tiles, {H} x {W} at tile {tile} has {(th, tw)}")
+    cnt = np.minimum(tile, H - tile * np.arange(th, dtype=np.int64))[:, None] * np.minimum(tile, W - tile * np.arange(tw, dtype=np.int64))[None, :]
+    m = (16 * sad) // (cnt << (8 if hdr else 0))
+    wt = np.where(m <= lo_q4, 0, np.where(m >= hi_q4, 256, ((m - lo_q4) * 256) // (hi_q4 - lo_q4))).astype(np.int64)
+    u, v = np.arange(W, dtype=np.int64) - tile // 2, np.arange(H, dtype=np.int64) - tile // 2
+    tx0, fx, ty0, fy = np.clip(u >> lg, 0, tw - 1), (u & (tile - 1))[None, None, :], np.clip(v >> lg, 0, th - 1), (v & (tile - 1))[None, :, None]
+    tx1, ty1 = np.clip((u >> lg) + 1, 0, tw - 1), np.clip((v >> lg) + 1, 0, th - 1)
+    pick = lambda ty, tx: wt[:, ty][:, :, tx]
+    w = ((tile - fx) * (tile - fy) * pick(ty0, tx0) + fx * (tile - fy) * pick(ty0, tx1) + (tile - fx) * fy * pick(ty1, tx0) + fx * fy * pick(ty1, tx1)
+         + tile * tile // 2) >> (2 * lg)
+    return wt, w
 
 
 SSIM_TILE_DTYPE = np.dtype([("sum_loss_q32", "<u8"), ("max_loss_q32", "<u8"), ("count", "<u4"), ("reserved", "<u4")])   # struct hf_ssim_tile

@@ -195,6 +195,7 @@ SIGNATURES = {
     "hf_frame_error_map_shape": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)]),
     "hf_frame_error_map_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "hf_warp_disagreement_map_enqueue": (_i, [_vp, _i, C.POINTER(C.c_float), _i, _vp]),
+    "hf_guarded_blend_enqueue": (_i, [_vp, _i, C.POINTER(C.c_float), _i, _i, _i, _vp, C.POINTER(_vp)]),
     "hf_frame_ssim_enqueue": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "hf_frame_ssim_read": (_i, [_vp, _i, _i, C.POINTER(HfFrameSsim)]),
     "hf_frame_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(HfFrameSsim)]),

@@ -616,17 +616,23 @@ int hf_warp_frames(hf_ctx* c, float t, int mode) {
     return HF_OK;
 }
 
+// The argument checks of hf_warp_disagreement_map_enqueue, for it and for the call that runs its launch first (`who`).
+static int check_disagreement_args(hf_ctx* c, const char* who, int n_t, const float* t, int tile, void* device_maps) {
+    if (!t) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null blending scalars", who);
+    if (n_t < 1 || n_t > HF_MAX_DISAGREEMENT_OUTPUTS) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: %d outputs, one launch takes 1 .. %d", who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS);
+    if (int rc = check_period_args(c, who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS, t, 0)) return rc;
+    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
+    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    return HF_OK;
+}
+
 // What hf_warp_frames would read at this moment -- frames N-2 / N-1 and the previous flow -- and where its modes 0 and 1 would disagree,
 // per tile; ordered like hf_frame_error_enqueue.  Nothing of the context moves: no output, no warp bookkeeping, no span, no counters.
 int hf_warp_disagreement_map_enqueue(hf_ctx* c, int n_t, const float* t, int tile, void* device_maps) {
     static_assert(HF_MAX_DISAGREEMENT_OUTPUTS == hf::kMaxDisagreementOutputs, "hopperflow.h");
     const char* who = "hf_warp_disagreement_map_enqueue";
     HF_CHECK_CTX(c);
-    if (!t) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null blending scalars", who);
-    if (n_t < 1 || n_t > HF_MAX_DISAGREEMENT_OUTPUTS) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: %d outputs, one launch takes 1 .. %d", who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS);
-    if (int rc = check_period_args(c, who, n_t, HF_MAX_DISAGREEMENT_OUTPUTS, t, 0)) return rc;
-    if (!HF_ERROR_MAP_TILES_OK(tile)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: tile %d, not 16, 32 or 64", who, tile);
-    if (!device_maps || ((uintptr_t)device_maps & 15u)) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: the map buffer %p is null or not 16-byte aligned", who, device_maps);
+    if (int rc = check_disagreement_args(c, who, n_t, t, tile, device_maps)) return rc;
     if (int rc = set_device(c)) return rc;
     if (int rc = leave_warp_stream(c)) return rc;
     hf::WarpPeriod p;
@@ -635,6 +641,28 @@ int hf_warp_disagreement_map_enqueue(hf_ctx* c, int n_t, const float* t, int til
         return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: nothing launched", who);
     HF_HIP(c, hipGetLastError());
     return note_launch(c, c->stream);   // a reader of the ring like the warps: the next asynchronous upload into frame N-2's slot waits for it
+}
+
+// The disagreement launch as above, then behind it on the same stream the blend that acts on it: per output the mode-2 frame of
+// hf_warp_frames mixed with the cross-fade of the two source frames by the weights of that output's map.  Same sources, order and state.
+int hf_guarded_blend_enqueue(hf_ctx* c, int n_t, const float* t, int tile, int lo_q4, int hi_q4, void* device_maps, void* const* device_out) {
+    const char* who = "hf_guarded_blend_enqueue";
+    HF_CHECK_CTX(c);
+    if (int rc = check_disagreement_args(c, who, n_t, t, tile, device_maps)) return rc;
+    if (lo_q4 < 0 || lo_q4 >= hi_q4 || hi_q4 > 65535) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: thresholds %d, %d outside 0 <= lo_q4 < hi_q4 <= 65535", who, lo_q4, hi_q4);
+    if (!device_out) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: null output frames", who);
+    for (int k = 0; k < n_t; k++) if (!device_out[k]) return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: output frame %d is null", who, k);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = leave_warp_stream(c)) return rc;
+    hf::WarpPeriod p;
+    fill_period(c, 0, nullptr, nullptr, p);
+    if (!hf::launch_warp_disagreement(c->g, p.frame12, p.frame21, p.flow, p.flow_xy, n_t, t, tile, device_maps, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: nothing launched", who);
+    HF_HIP(c, hipGetLastError());
+    if (!hf::launch_guarded_blend(c->g, p.frame12, p.frame21, p.flow, p.flow_xy, n_t, t, tile, lo_q4, hi_q4, device_maps, device_out, p.black, p.white, c->stream))
+        return fail(c, HF_ERR_INVALID_ARGUMENT, "%s: nothing launched", who);
+    HF_HIP(c, hipGetLastError());
+    return note_launch(c, c->stream);
 }
 
 int hf_copy_frame(hf_ctx* c) {

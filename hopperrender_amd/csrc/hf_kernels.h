@@ -180,6 +180,13 @@ void launch_warp(const Geom& g, const void* frame12, const void* frame21, const 
 constexpr int kMaxDisagreementOutputs = 24;
 bool launch_warp_disagreement(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
                               int n_t, const float* t, int tile, void* maps, hipStream_t stream);
+// Guarded blend (hf_kernels.hip; hf_guarded_blend_enqueue): behind launch_warp_disagreement with the same sources, t and tile on the same
+// stream, into outs[k] (a frame of g.out_stride each) the mode-2 output of launch_warp at t[k] mixed with the cross-fade by the weights
+// that map k's luma sad and the thresholds give.  One launch per chunk of kMaxWarpOutputs outputs.  black/white already scaled for HDR.
+// false: nothing launched (n_t, tile or thresholds out of range).
+bool launch_guarded_blend(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
+                          int n_t, const float* t, int tile, int lo_q4, int hi_q4, const void* maps, void* const* outs,
+                          float black, float white, hipStream_t stream);
 // copyFrameKernel, both planes in one launch.
 void launch_copy(const Geom& g, const void* src, void* out, float black, float white, hipStream_t stream);
 // Planar 4:2:0 frames at the device boundary (hf_planar.hip; HF_FLAG_PLANAR_IN / HF_FLAG_PLANAR_OUT): planar (Y, U, V planes) <-> the

@@ -675,7 +675,9 @@ __device__ __forceinline__ void warp_finish(const WarpSrc<E, GROUP, ROWS, (VB / 
 // SINK (warp_disagreement_kernel, MODE 2): instead of blending and storing, every element's two raw samples -- what MODE 0 and MODE 1
 // would store there -- go to sink.add(element within the thread's row, a, b), and sink.flush(ti) ends output ti; nothing is written.
 // SINK::each: every element takes the path of the ragged right edge, through warp_element.
-struct WarpStore { static constexpr bool each = false; };
+// SINK::blended (guarded_blend_run_kernel): the sink takes the BLENDED output instead -- sink.row(ti, row, the VB bytes warp_finish would
+// store there), or at the ragged right edge sink.element(ti, row, element, what warp_element returns in MODE 2).
+struct WarpStore { static constexpr bool each = false, blended = false; };
 template <typename E, int GROUP, int ROWS, int MODE, int CZ, int VB, bool DW, typename SINK = WarpStore>
 __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a, int cy0, int cx0, int ti0, int ti1, SINK* sink = nullptr) {
     constexpr bool kStore = std::is_same<SINK, WarpStore>::value;
@@ -697,6 +699,9 @@ __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a,
                 E* __restrict__ o = (E*)at.out + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
                 for (int r = 0; r < nrows; r++)
                     for (int i = 0; i < VEC && cx0 + i < W; i++) o[(size_t)r * So + i] = (E)warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r);
+            } else if constexpr (SINK::blended) {
+                for (int r = 0; r < nrows; r++)
+                    for (int i = 0; i < VEC && cx0 + i < W; i++) sink->element(ti, r, i, warp_element<E>(g, at, lv, CZ, cx0 + i, cy0 + r));
             } else {
                 for (int r = 0; r < nrows; r++)
                     for (int i = 0; i < VEC && cx0 + i < W; i++) {
@@ -900,6 +905,8 @@ __device__ __forceinline__ void warp_fast_body(const Geom& g, const WarpArgs& a,
     if constexpr (kStore) {
         E* __restrict__ out = (E*)a.outv[ti] + (size_t)CZ * H * So + (size_t)cy0 * So + cx0;
         warp_finish<E, GROUP, ROWS, MODE, CZ, VB>(S, a.s12v[ti], a.s21v[ti], out, So, nrows, lv);
+    } else if constexpr (SINK::blended) {
+        warp_finish_to<E, GROUP, ROWS, MODE, CZ, VB>(S, a.s12v[ti], a.s21v[ti], nrows, lv, [&](const int r, const E* v) { sink->row(ti, r, v); });
     } else {
 #pragma unroll
         for (int r = 0; r < ROWS; r++) {
@@ -1017,7 +1024,7 @@ static_assert(sizeof(Geom) + sizeof(DisagreeArgs) <= 4096, "kernel arguments: 4 
 
 template <typename E, int CZ, bool EACH>
 struct DisagreeSink {
-    static constexpr bool each = EACH;
+    static constexpr bool each = EACH, blended = false;
     using Sq = typename std::conditional<sizeof(E) == 1, uint32_t, unsigned long long>::type;   // 32 8-bit squares fit 32 bits, two 16-bit ones do not
     DisTile (*acc)[3][kDisStripTiles];
     int txl;                         // the item's tile within the strip
@@ -1088,6 +1095,186 @@ __global__ __launch_bounds__(kDisBlock) void warp_disagreement_kernel(const Geom
             }
         }
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Guarded blend (hf_guarded_blend_enqueue; the definition is in include/hopperflow.h)
+// ------------------------------------------------------------------------------------------
+// G = (M (256 - w) + Z w + 128) >> 8 per element: M the motion-compensated blend (mode 2, levels included), Z the cross-fade (the same
+// element under a zero flow), w the bilinearly interpolated tile weight from the luma sad of the disagreement maps, which the launch
+// before this one stored.  One launch per CHUNK of up to kMaxWarpOutputs outputs (the WarpArgs of a fused period; 24 outputs: four
+// launches, Geom + GuardArgs are far below the 4 KB of kernel arguments).  Two kernels:
+//   guarded_blend_run_kernel   M from warp_fast_body -- its flow lookups once per chunk, its run loaders, its blend (warp_finish_to) --
+//                              through a sink that takes the blended rows (SINK::blended) in place of the store; wherever the fused
+//                              period warp's run kernel with 16 bytes per thread applies (warp_fast_shape).  A workgroup is 8 rows of ONE
+//                              plane by 64 store groups of 16 bytes, a thread one store group by two rows of one flow-cell row.
+//   guarded_blend_kernel       every element through warp_element, mapped like warp_kernel (4 rows by 64 store groups): rs = 0, odd
+//                              strides, frames too narrow for a run, a t below 0, unaligned outputs.  The same integers.
+// Weights.  The rows of a workgroup lie between at most three rows of tile centres (two for four rows starting at a multiple of four, and
+// for eight luma rows; three for eight chroma rows at tile 16) and its columns between at most 64 * VEC / tile + 2 columns of them: those
+// tiles' weights, per output of the chunk, go into LDS at the workgroup's start, the index clamped THERE -- the only divisions of the
+// kernels, in 32 bits: 16 sad / (cnt << 8) = sad / (cnt << 4) in HDR, 16 sad < 2^25 in SDR, m <= 4095.  Per element: the vertical mix of
+// two rows, the horizontal mix, a shift.
+// Traffic per output: the two gathered source frames and the stored frame, 3F, where no weight of a store group is nonzero; the two
+// cross-fade samples are loaded only in groups where one is, up to 5F when every group does.  (w = 0 leaves M as it is either way.)
+constexpr int kGuardBlock = 256, kGuardRows = 4, kGuardRunRows = 8, kGuardTileRows = 3;
+constexpr int kGuardCols = 64 * 16 / 16 + 2;     // SDR at tile 16
+
+struct GuardArgs {
+    WarpArgs a;                      // the chunk: frames, flow, levels, n_out, s12v, s21v, outv; mode 2
+    const uint32_t* maps;            // hf_error_tile [n_t][3][th][tw] as four words each: sse lo, sse hi, sad, max
+    int first;                       // the chunk's first output among the n_t maps
+    int tile, lg, tw, th;
+    int lo_q4, hi_q4;
+    size_t entries;                  // n_t 3 th tw (debug-bounds)
+};
+static_assert(sizeof(Geom) + sizeof(GuardArgs) <= 4096, "kernel arguments: 4 KB");
+
+typedef uint16_t GuardLds[kMaxWarpOutputs][kGuardTileRows][kGuardCols];
+
+// The weights of tile rows tyb .. tyb + n_rows - 1 and tile columns tb .. tb + ncols - 1 (both clamped to the grid) of the chunk's outputs.
+template <bool HDR>
+__device__ __forceinline__ void guard_fill_weights(GuardLds& wt, const Geom& g, const GuardArgs& d, int tb, int tyb, int n_rows, int ncols) {
+    const int tile = d.tile;
+    for (int e = threadIdx.x; e < d.a.n_out * n_rows * ncols; e += kGuardBlock) {
+        const int j = e % ncols, q = e / ncols, ry = q % n_rows, ti = q / n_rows;
+        const int tx = clampi(tb + j, 0, d.tw - 1), ty = clampi(tyb + ry, 0, d.th - 1);
+        const size_t at = ((size_t)(d.first + ti) * 3u * (size_t)d.th + (size_t)ty) * (size_t)d.tw + (size_t)tx;   // plane 0: luma
+        HF_DBG_CHECK(at < d.entries && j < kGuardCols && ry < kGuardTileRows && ti < kMaxWarpOutputs, 290);
+        const uint32_t sad = d.maps[at * 4u + 2u];
+        const uint32_t cnt = (uint32_t)(min(tile, g.W - tx * tile) * min(tile, g.H - ty * tile));
+        const int m = (int)(HDR ? sad / (cnt << 4) : (sad << 4) / cnt);
+        wt[ti][ry][j] = (uint16_t)(m <= d.lo_q4 ? 0 : m >= d.hi_q4 ? 256 : ((m - d.lo_q4) * 256) / (d.hi_q4 - d.lo_q4));
+    }
+}
+
+// The weight of the element at luma column xl in a row whose upper tile row is LDS row ry0, fy of a tile below that row's centres.
+__device__ __forceinline__ unsigned guard_weight(const GuardLds& wt, const GuardArgs& d, int ti, int ry0, int fy, int xl, int tb) {
+    const int tile = d.tile, u = xl - (tile >> 1);
+    const int j0 = (u >> d.lg) - tb, fx = u & (tile - 1);
+    HF_DBG_CHECK(j0 >= 0 && j0 + 1 < kGuardCols && ry0 >= 0 && ry0 + 1 < kGuardTileRows, 291);
+    const unsigned c0 = (unsigned)(tile - fy) * wt[ti][ry0][j0] + (unsigned)fy * wt[ti][ry0 + 1][j0];
+    const unsigned c1 = (unsigned)(tile - fy) * wt[ti][ry0][j0 + 1] + (unsigned)fy * wt[ti][ry0 + 1][j0 + 1];
+    return ((unsigned)(tile - fx) * c0 + (unsigned)fx * c1 + (unsigned)(tile * tile >> 1)) >> (2 * d.lg);
+}
+
+// What warp_element returns in mode 2 where the flow is zero: both samples at the mirrored position itself.
+template <typename E>
+__device__ __forceinline__ unsigned crossfade_element(const Geom& g, const WarpArgs& a, float s12, float s21, const Levels& lv, int cz, int cx, int cy) {
+    const E* __restrict__ A = (const E*)a.frame12;
+    const E* __restrict__ B = (const E*)a.frame21;
+    const int dim_y = cz ? (g.H >> 1) : g.H;
+    const int x = mirror_warp(cx, g.W), y = mirror_warp(cy, dim_y);
+    HF_DBG_CHECK(x >= 0 && y >= 0 && y < dim_y && (cz ? (x & ~1) + 1 : x) < g.W, 293);
+    const size_t at = (size_t)cz * g.H * g.in_stride + (size_t)y * g.in_stride + (cz ? (x & ~1) + (cx & 1) : x);
+    const unsigned blended = (unsigned)__builtin_fmaf((float)A[at], s21, (float)B[at] * s12) & 0xFFFFu;
+    return cz ? levels_uv<E>((float)blended, lv) : levels_y<E>((float)blended, lv);
+}
+
+// One store group of one row of output ti: the weights, the cross-fade where one is nonzero, the mix, the store.  m: the n <= VEC blended
+// elements (n < VEC, or !WIDE: element stores).
+template <typename E, int CZ, bool WIDE>
+__device__ __forceinline__ void guard_store_group(const Geom& g, const GuardArgs& d, const GuardLds& wt, const Levels& lv, int ti, int tb, int tyb,
+                                                  int cx0, int cy, int n, const E* m) {
+    constexpr int VEC = 16 / (int)sizeof(E);
+    const int So = g.out_stride, u = (CZ ? 2 * cy : cy) - (d.tile >> 1);
+    const int ry0 = (u >> d.lg) - tyb, fy = u & (d.tile - 1);
+    const float s12 = d.a.s12v[ti], s21 = d.a.s21v[ti];
+    unsigned w[VEC], any = 0;
+#pragma unroll
+    for (int i = 0; i < VEC; i++) {
+        const int x = cx0 + (i < n ? i : 0);
+        w[i] = guard_weight(wt, d, ti, ry0, fy, CZ ? (x & ~1) : x, tb);
+        any |= i < n ? w[i] : 0u;
+    }
+    __attribute__((aligned(16))) E v[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; i++) {
+        unsigned r = i < n ? m[i] : 0u;
+        if (any && i < n) r = (r * (256u - w[i]) + crossfade_element<E>(g, d.a, s12, s21, lv, CZ, cx0 + i, cy) * w[i] + 128u) >> 8;
+        v[i] = (E)r;
+    }
+    const size_t o0 = (size_t)CZ * g.H * So + (size_t)cy * So + cx0;
+    HF_DBG_CHECK(cx0 >= 0 && cy >= 0 && cy < (CZ ? g.H >> 1 : g.H) && cx0 + n <= g.W && o0 + n <= (size_t)So * (g.H + (g.H >> 1)), 292);
+    E* __restrict__ out = (E*)d.a.outv[ti] + o0;
+    if (WIDE && n == VEC) store16_streaming(out, v);
+    else {
+#pragma unroll
+        for (int i = 0; i < VEC; i++) if (i < n) out[i] = v[i];
+    }
+}
+
+template <typename E, bool ALIGNED>
+__global__ __launch_bounds__(kGuardBlock) void guarded_blend_kernel(const Geom g, const GuardArgs d) {
+    constexpr int VEC = 16 / (int)sizeof(E);
+    __shared__ GuardLds wt;
+    const int H = g.H, W = g.W, half = d.tile >> 1;
+    const int ny = (H + kGuardRows - 1) / kGuardRows;           // blockIdx.y: the luma blocks, then the chroma blocks
+    const int cz = (int)blockIdx.y >= ny;
+    const int r0 = ((int)blockIdx.y - (cz ? ny : 0)) * kGuardRows;
+    const int dim_y = cz ? (H >> 1) : H;
+    const int bx0 = (int)blockIdx.x * 64 * VEC;                 // a multiple of every tile
+    const int tb = (bx0 - half) >> d.lg;                        // the tile column of LDS column 0 (-1 at the left edge), arithmetic shifts
+    const int tyb = ((cz ? 2 * r0 : r0) - half) >> d.lg;
+    guard_fill_weights<sizeof(E) == 2>(wt, g, d, tb, tyb, 2, ((64 * VEC) >> d.lg) + 2);
+    __syncthreads();
+    const int cy = r0 + (int)(threadIdx.x >> 6);
+    const int cx0 = bx0 + (int)(threadIdx.x & 63) * VEC;
+    if (cy >= dim_y || cx0 >= W) return;
+    const int n = min(VEC, W - cx0);
+    const Levels lv = make_levels(d.a.black, d.a.white);
+    for (int ti = 0; ti < d.a.n_out; ti++) {
+        WarpArgs at = d.a;
+        at.s12 = d.a.s12v[ti]; at.s21 = d.a.s21v[ti];
+        E m[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; i++) m[i] = i < n ? (E)warp_element<E>(g, at, lv, cz, cx0 + i, cy) : (E)0;
+        if (cz) guard_store_group<E, 1, ALIGNED>(g, d, wt, lv, ti, tb, tyb, cx0, cy, n, m);
+        else guard_store_group<E, 0, ALIGNED>(g, d, wt, lv, ti, tb, tyb, cx0, cy, n, m);
+    }
+}
+
+template <typename E, int CZ>
+struct GuardSink {
+    static constexpr bool each = false, blended = true;
+    static constexpr int VEC = 16 / (int)sizeof(E);
+    const Geom& g;
+    const GuardArgs& d;
+    const GuardLds& wt;
+    Levels lv;
+    int tb, tyb, cx0, cy0;
+    __device__ __forceinline__ void row(int ti, int r, const E* v) { guard_store_group<E, CZ, true>(g, d, wt, lv, ti, tb, tyb, cx0, cy0 + r, VEC, v); }
+    __device__ __forceinline__ void element(int ti, int r, int i, unsigned v) {   // the ragged right edge: one element a call
+        const E m = (E)v;
+        guard_store_group<E, CZ, false>(g, d, wt, lv, ti, tb, tyb, cx0 + i, cy0 + r, 1, &m);
+    }
+};
+
+template <typename E, int GROUP, bool DW>
+__global__ __launch_bounds__(kGuardBlock) void guarded_blend_run_kernel(const Geom g, const GuardArgs d) {
+    constexpr int VEC = 16 / (int)sizeof(E);
+    __shared__ GuardLds wt;
+    const int H = g.H, W = g.W, half = d.tile >> 1;
+    const int ny = (H + kGuardRunRows - 1) / kGuardRunRows;     // blockIdx.y: the luma blocks, then the chroma blocks
+    const int cz = (int)blockIdx.y >= ny;
+    const int r0 = ((int)blockIdx.y - (cz ? ny : 0)) * kGuardRunRows;
+    const int bx0 = (int)blockIdx.x * 64 * VEC;
+    const int tb = (bx0 - half) >> d.lg;
+    const int tyb = ((cz ? 2 * r0 : r0) - half) >> d.lg;
+    guard_fill_weights<sizeof(E) == 2>(wt, g, d, tb, tyb, kGuardTileRows, ((64 * VEC) >> d.lg) + 2);
+    __syncthreads();
+    const int cy0 = r0 + (int)(threadIdx.x >> 6) * 2;           // two rows of one flow-cell row
+    const int cx0 = bx0 + (int)(threadIdx.x & 63) * VEC;
+    if (cy0 >= (cz ? (H >> 1) : H) || cx0 >= W) return;
+    const Levels lv = make_levels(d.a.black, d.a.white);
+    // (the gathers themselves are warp_fast_body's and warp_element's, with their sites 201 .. 209)
+    if (cz) {
+        GuardSink<E, 1> sink{g, d, wt, lv, tb, tyb, cx0, cy0};
+        warp_fast_body<E, GROUP, 2, 2, 1, 16, DW>(g, d.a, cy0, cx0, 0, d.a.n_out, &sink);
+    } else {
+        GuardSink<E, 0> sink{g, d, wt, lv, tb, tyb, cx0, cy0};
+        warp_fast_body<E, GROUP, 2, 2, 0, 16, DW>(g, d.a, cy0, cx0, 0, d.a.n_out, &sink);
     }
 }
 
@@ -1697,6 +1884,57 @@ bool launch_warp_disagreement(const Geom& g, const void* frame12, const void* fr
                     (((uintptr_t)frame12 | (uintptr_t)frame21) & 3) == 0;
     if (g.hdr) dispatch_warp_disagreement<uint16_t>(g, d, runs, dw, stream);
     else dispatch_warp_disagreement<uint8_t>(g, d, runs, dw, stream);
+    return true;
+}
+
+template <typename E>
+static void dispatch_guarded_blend(const Geom& g, const GuardArgs& d, bool runs, bool dw, bool aligned, hipStream_t stream) {
+    constexpr int V16 = 16 / (int)sizeof(E);
+    const dim3 blk(kGuardBlock);
+    const unsigned gx = (unsigned)((g.W + 64 * V16 - 1) / (64 * V16));
+    const auto gy = [&](int rows) { return (unsigned)((g.H + rows - 1) / rows + ((g.H >> 1) + rows - 1) / rows); };
+#define HF_GUARD_RUN(G) do { if (dw) HF_LAUNCH("guarded_blend", (guarded_blend_run_kernel<E, G, true>), dim3(gx, gy(kGuardRunRows)), blk, 0, stream, g, d); \
+                             else HF_LAUNCH("guarded_blend", (guarded_blend_run_kernel<E, G, false>), dim3(gx, gy(kGuardRunRows)), blk, 0, stream, g, d); } while (0)
+    const int g16 = warp_group(g, 16);
+    if (runs && g16 == V16) HF_GUARD_RUN(V16);
+    else if (runs && g16 == V16 / 2) HF_GUARD_RUN(V16 / 2);
+    else if (runs && g16 == V16 / 4) HF_GUARD_RUN(V16 / 4);
+    else if (aligned) HF_LAUNCH("guarded_blend", (guarded_blend_kernel<E, true>), dim3(gx, gy(kGuardRows)), blk, 0, stream, g, d);
+    else HF_LAUNCH("guarded_blend", (guarded_blend_kernel<E, false>), dim3(gx, gy(kGuardRows)), blk, 0, stream, g, d);
+#undef HF_GUARD_RUN
+}
+
+bool launch_guarded_blend(const Geom& g, const void* frame12, const void* frame21, const int16_t* flow, const uint32_t* flow_xy,
+                          int n_t, const float* t, int tile, int lo_q4, int hi_q4, const void* maps, void* const* outs,
+                          float black, float white, hipStream_t stream) {
+    if (n_t < 1 || n_t > kMaxDisagreementOutputs || (tile != 16 && tile != 32 && tile != 64) || lo_q4 < 0 || lo_q4 >= hi_q4) return false;
+    const int vec = 16 / (int)elem_size(g);
+    GuardArgs d{};
+    d.maps = static_cast<const uint32_t*>(maps);
+    d.tile = tile; d.lg = tile == 16 ? 4 : tile == 32 ? 5 : 6;
+    d.tw = (g.W + tile - 1) / tile; d.th = (g.H + tile - 1) / tile;
+    d.lo_q4 = lo_q4; d.hi_q4 = hi_q4;
+    d.entries = (size_t)n_t * 3u * (size_t)d.th * (size_t)d.tw;
+    WarpArgs& a = d.a;
+    a.frame12 = frame12; a.frame21 = frame21; a.flow = flow; a.flow_xy = flow_xy;
+    a.mode = 2; a.black = black; a.white = white;
+    for (int c = 0; c < n_t; c += kMaxWarpOutputs) {   // one launch per chunk of outputs
+        d.first = c;
+        a.n_out = n_t - c < kMaxWarpOutputs ? n_t - c : kMaxWarpOutputs;
+        WarpPeriod p{};                                  // the chunk as the fused period warp would be handed it: does its run kernel apply?
+        p.frame12 = frame12; p.frame21 = frame21; p.flow = flow; p.flow_xy = flow_xy; p.black = black; p.white = white; p.n_out = a.n_out;
+        bool aligned = (g.out_stride % vec) == 0;
+        for (int i = 0; i < a.n_out; i++) {
+            a.s12v[i] = t[c + i]; a.s21v[i] = 1.0f - t[c + i]; a.outv[i] = outs[c + i];
+            p.ts[i] = t[c + i]; p.outs[i] = outs[c + i];
+            aligned = aligned && ((uintptr_t)outs[c + i] & 15) == 0;
+        }
+        a.s12 = a.s12v[0]; a.s21 = a.s21v[0]; a.out = a.outv[0];
+        bool dw = false;
+        const bool runs = warp_fast_shape(g, 1, &p, 2, 16, dw);
+        if (g.hdr) dispatch_guarded_blend<uint16_t>(g, d, runs, dw, aligned, stream);
+        else dispatch_guarded_blend<uint8_t>(g, d, runs, dw, aligned, stream);
+    }
     return true;
 }
 

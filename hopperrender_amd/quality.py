@@ -77,7 +77,17 @@ submitted once more.  The report has per period the pair, the t's and per t and 
 the worst tile; per clip the plane totals, the worst (period, t) by the rms of Y and the per-period mean rms of Y as a list.  The maps
 are read once per chunk, a chunk being the periods whose maps fit CONFIDENCE_MAP_BYTES and whose sources fit CONFIDENCE_SOURCE_BYTES.
 On the command line --confidence takes the flow settings, --disagreement TILE and --sweep; the options of the leave-one-out run
-(--ssim, --map, --ssim-map, --map-dir, --detect-cuts, --black, --white) are refused beside it.
+(--ssim, --map, --ssim-map, --map-dir, --guard, --detect-cuts, --black, --white) are refused beside it.
+
+--guard TILE:LO:HI / evaluate(guard=(tile, lo_q4, hi_q4)) asks whether ACTING on that confidence helps on this clip: straight behind each
+evaluated pair's period the withheld frame is produced a second time by hf_guarded_blend_enqueue at t = 0.5 (the blend, faded into the
+plain cross-fade of the two source frames where a tile's mean luma disagreement lies between LO and HI sixteenths of an 8-bit code) and
+judged against the same truth by every metric the run asked for.  Each pair gains "guarded" -- the plane dicts of "interpolated", with
+"map" / "ssim_map" where those run, and "mask": tiles, tiles_firing (tile weight above 0) and mean_weight (0 .. 1 over the luma
+pixels) -- and "guard_gain_db", guarded minus plain PSNR of Y (with --ssim also "guard_gain_ssim"); the clip gains the same from the
+summed errors, and the report "guard".  A chunk then holds two thirds of the pairs (a third result slot each).  With --map-dir the luma
+mask of every pair is written as guard_pair0001.pgm ..., one pixel per luma pixel, min(w, 255).  There are no default thresholds:
+nobody has measured good ones; (4080, 4081) is guard off.  Without the option none of this is called, allocated or reported.
 """
 import argparse
 import itertools
@@ -298,8 +308,22 @@ def _minus(a, b):
     return None if a is None or b is None else a - b
 
 
+def parse_guard(spec):
+    """"TILE:LO:HI" (the command line) or a sequence of three -> (tile, lo_q4, hi_q4) as hf_guarded_blend_enqueue takes them; ValueError otherwise"""
+    parts = spec.split(":") if isinstance(spec, str) else list(spec)
+    try:
+        tile, lo, hi = (int(str(x), 10) for x in parts)
+    except (TypeError, ValueError):
+        raise ValueError(f"guard {spec!r}: TILE:LO:HI, three integers (for example 16:32:96)") from None
+    if tile not in (16, 32, 64):
+        raise ValueError(f"guard {spec!r}: tile {tile}, not 16, 32 or 64")
+    if not 0 <= lo < hi <= 65535:
+        raise ValueError(f"guard {spec!r}: thresholds outside 0 <= LO < HI <= 65535 (sixteenths of an 8-bit code of mean luma difference)")
+    return tile, lo, hi
+
+
 def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=False, scene_threshold=200, source_frame_time=417083,
-             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, ssim_map=0, disagreement=0, **settings):
+             device_index=0, device=None, ssim=False, error_map=0, map_dir=None, ssim_map=0, disagreement=0, guard=None, **settings):
     """Leave-one-out evaluation of `frames` (a sequence of flat NV12 uint8 / P010 uint16 host frames of H x W, stride W) -> report dict.
     settings: search_radius, delta_scalar, neighbor_scalar, blur_radius, iterations, max_calc_res (defaults: SETTINGS; 0 = the
     library's default for blur_radius and iterations).  detect_scene_cuts: also report the warp / copy decision the filter's
@@ -310,15 +334,18 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
     called, allocated or reported.  disagreement: 16, 32 or 64 -- also the warp disagreement map of every evaluated pair at t = 0.5, the
     judge that needs no truth, and beside error_map of the same tile how well it predicts the real error (module docstring); 0, nothing
     of it is called, allocated or reported.  map_dir: with error_map, ssim_map or disagreement, a directory for one PGM heat map of the
-    Y plane per evaluated pair and map."""
+    Y plane per evaluated pair and map.  guard: (tile, lo_q4, hi_q4) -- every withheld frame is produced a second time by the guarded blend
+    (module docstring) and judged by the same metrics beside the plain one; None, nothing of it is called, allocated or reported."""
+    if guard is not None:
+        guard = parse_guard(guard)
     if error_map not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: error_map {error_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
     if ssim_map not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: ssim_map {ssim_map}, a tile of 16, 32 or 64 luma pixels (0: none)")
     if disagreement not in (0, 16, 32, 64):
         raise ValueError(f"evaluate: disagreement {disagreement}, a tile of 16, 32 or 64 luma pixels (0: none)")
-    if map_dir and not error_map and not ssim_map and not disagreement:
-        raise ValueError("evaluate: map_dir needs error_map, ssim_map or disagreement")
+    if map_dir and not error_map and not ssim_map and not disagreement and not guard:
+        raise ValueError("evaluate: map_dir needs error_map, ssim_map, disagreement or guard")
     unknown = set(settings) - set(SETTINGS)
     if unknown:
         raise TypeError(f"evaluate: unknown settings {sorted(unknown)} (known: {sorted(SETTINGS)})")
@@ -346,6 +373,21 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         from .calc import frame_error_maps
         dtiles_x, dtiles_y, dmap_bytes = main.frameErrorMapShape(disagreement)
         dis_buf = dev.buffer(dmap_bytes * min(PAIRS_PER_READ, sum(s["evaluated"] for s in sched)))
+    # guard: per chunk fewer pairs, a third result slot each behind the two of every pair; its maps (the confidence the call stores, and
+    # those of the metrics asked for) in buffers of their own
+    per_read = max(1, PAIRS_PER_READ * 2 // 3) if guard else PAIRS_PER_READ
+    gbase = 2 * per_read
+    gdis_buf = gmaps_buf = gsmaps_buf = None
+    luma_masks = []
+    if guard:
+        from .calc import frame_error_maps, guard_weights
+        n_maps = min(per_read, sum(s["evaluated"] for s in sched))
+        gtiles_x, gtiles_y, gdis_bytes = main.frameErrorMapShape(guard[0])
+        gdis_buf = dev.buffer(gdis_bytes * n_maps)
+        if error_map:
+            gmaps_buf = dev.buffer(map_bytes * n_maps)
+        if ssim_map:
+            gsmaps_buf = dev.buffer(smap_bytes * n_maps)
     take = lambda pool, nbytes: pool.pop() if pool else dev.buffer(nbytes)
     src = {}    # period -> device frame of its source; the last three outlive a chunk (the context's ring still references them)
     try:
@@ -353,7 +395,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         while todo:
             # a chunk: the periods up to PAIRS_PER_READ evaluated pairs
             chunk, n_eval = [], 0
-            while todo and n_eval < PAIRS_PER_READ:
+            while todo and n_eval < per_read:
                 chunk.append(todo.pop(0))
                 n_eval += chunk[-1]["evaluated"]
             used_in, used_out = [], []
@@ -361,7 +403,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
             for s in chunk:
                 src[s["period"]] = take(free_in, frame_bytes)
                 src[s["period"]].upload(frames[s["source_frame"]])
-            jobs = {}
+            jobs, gouts = {}, {}
             for s in (s for s in chunk if s["evaluated"]):
                 t_raw = take(free_in, frame_bytes)
                 t_raw.upload(frames[s["truth_frame"]])
@@ -374,6 +416,9 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     aux.updateFrameDevice(raw.ptr)
                     aux.copyFrame()
                 jobs[s["period"]] = (truth, repeat, out)
+                if guard:
+                    gouts[s["period"]] = take(free_out, out_bytes)
+                    used_out.append(gouts[s["period"]])
             aux.sync()
             # the clip: periods and comparisons back to back, nothing waits on the host (unless the caller asked for the cut decisions)
             scratch = take(free_out, out_bytes)     # where the warm-up pair's output goes
@@ -399,6 +444,16 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                     if ssim_map:
                         main.frameSsimMapEnqueue([out.ptr], [truth.ptr], ssim_map, smaps_buf.ptr + (slot // 2) * smap_bytes)
                     slot += 2
+                if s["evaluated"] and guard:        # the same frames and flow again, still ahead of the next period; judged like `out`
+                    i, gout = slot // 2 - 1, gouts[s["period"]]
+                    main.guardedBlendEnqueue([0.5], guard[0], guard[1], guard[2], gdis_buf.ptr + i * gdis_bytes, [gout.ptr])
+                    main.frameErrorEnqueue([gout.ptr], [truth.ptr], gbase + i)
+                    if ssim:
+                        main.frameSsimEnqueue([gout.ptr], [truth.ptr], gbase + i)
+                    if error_map:
+                        main.frameErrorMapEnqueue([gout.ptr], [truth.ptr], error_map, gmaps_buf.ptr + i * map_bytes)
+                    if ssim_map:
+                        main.frameSsimMapEnqueue([gout.ptr], [truth.ptr], ssim_map, gsmaps_buf.ptr + i * smap_bytes)
                 if filt is not None:
                     main.waitFlow()
                     fc, delta = int(main.m_frameCount), int(main.m_totalFrameDelta)
@@ -416,6 +471,16 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
             if disagreement and slot:
                 import numpy as np
                 got_dis = frame_error_maps(dis_buf.download(np.uint8, (slot // 2) * dmap_bytes), slot // 2, dtiles_x, dtiles_y)
+            if guard and slot:
+                import numpy as np
+                n = slot // 2
+                got_g = main.frameErrorRead(gbase, n)
+                got_gssim = main.frameSsimRead(gbase, n) if ssim else []
+                got_gdis = frame_error_maps(gdis_buf.download(np.uint8, n * gdis_bytes), n, gtiles_x, gtiles_y)
+                if error_map:
+                    got_gmaps = frame_error_maps(gmaps_buf.download(np.uint8, n * map_bytes), n, tiles_x, tiles_y)
+                if ssim_map:
+                    got_gsmaps = frame_ssim_maps(gsmaps_buf.download(np.uint8, n * smap_bytes), n, stiles_x, stiles_y)
             for i, s in enumerate(s for s in chunk if s["evaluated"]):
                 row = {"pair": s["pair"], "period": s["period"], "source_frames": [2 * s["pair"], 2 * s["pair"] + 2],
                        "withheld_frame": s["truth_frame"], "interpolated": _with_psnr(got[2 * i], peak), "repeat": _with_psnr(got[2 * i + 1], peak)}
@@ -440,6 +505,20 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
                         overlaps.append(over)
                     if map_dir:
                         luma_dis.append((s["pair"], got_dis[i][0].copy()))
+                if guard:
+                    g = row["guarded"] = _with_psnr(got_g[i], peak)
+                    row["guard_gain_db"] = _minus(g["Y"]["psnr"], row["interpolated"]["Y"]["psnr"])
+                    if ssim:
+                        _add_ssim(g, got_gssim[i])
+                        row["guard_gain_ssim"] = _minus(g["Y"]["ssim"], row["interpolated"]["Y"]["ssim"])
+                    if error_map:
+                        g["map"] = _map_dict(got_gmaps[i], error_map)
+                    if ssim_map:
+                        g["ssim_map"] = _ssim_map_dict(got_gsmaps[i], ssim_map, got_gmaps[i] if error_map == ssim_map else None)
+                    wt, w = guard_weights(got_gdis[i:i + 1], guard[0], guard[1], guard[2], H, W, hdr)
+                    g["mask"] = {"tiles": int(wt.size), "tiles_firing": int(np.count_nonzero(wt)), "mean_weight": float(w.mean()) / 256.0}
+                    if map_dir:
+                        luma_masks.append((s["pair"], np.minimum(w[0], 255).astype(np.uint8)))
                 rows.append(row)
             # everything has finished: the chunk's buffers can be used again, but for the three sources the ring still references
             last = chunk[-1]["period"]
@@ -450,7 +529,7 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         aux.close()
         if filt is not None:
             filt.close()
-        for b in free_in + free_out + list(src.values()) + [b for b in (maps_buf, smaps_buf, dis_buf) if b is not None]:
+        for b in free_in + free_out + list(src.values()) + [b for b in (maps_buf, smaps_buf, dis_buf, gdis_buf, gmaps_buf, gsmaps_buf) if b is not None]:
             b.free()
     worst = min(rows, key=lambda r: float("inf") if r["interpolated"]["Y"]["psnr"] is None else r["interpolated"]["Y"]["psnr"])
     clip = {"interpolated": _aggregate(rows, "interpolated", peak), "repeat": _aggregate(rows, "repeat", peak),
@@ -491,10 +570,28 @@ def evaluate(frames, hdr, H, W, *, black=0.0, white=255.0, detect_scene_cuts=Fal
         clip["worst_tile_disagreement"] = {"pair": top["pair"], "plane": "Y", "x": t["x"], "y": t["y"], "sse": t["sse"]}
         if map_dir:
             _write_map_pgms(map_dir, luma_dis, disagreement, H, W, prefix="dis")
-    return {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
-            "settings": dict(st, black_level=float(black), white_level=float(white)),
-            "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
-            "pairs": rows, "clip": clip, "scene_cuts": cuts if detect_scene_cuts else None}
+    if guard:
+        clip["guarded"] = _aggregate(rows, "guarded", peak)
+        clip["guard_gain_db"] = _minus(clip["guarded"]["Y"]["psnr"], clip["interpolated"]["Y"]["psnr"])
+        if ssim:
+            _add_ssim_aggregate(clip["guarded"], rows, "guarded")
+            clip["guard_gain_ssim"] = _minus(clip["guarded"]["Y"]["ssim"], clip["interpolated"]["Y"]["ssim"])
+        clip["guarded"]["mask"] = {"tiles": sum(r["guarded"]["mask"]["tiles"] for r in rows),
+                                   "tiles_firing": sum(r["guarded"]["mask"]["tiles_firing"] for r in rows),
+                                   "mean_weight": sum(r["guarded"]["mask"]["mean_weight"] for r in rows) / len(rows)}
+        if map_dir:
+            os.makedirs(map_dir, exist_ok=True)
+            for pair, w in luma_masks:              # the luma mask itself, one pixel per luma pixel: 0 .. 255 = min(w, 255)
+                with open(os.path.join(map_dir, f"guard_pair{pair:04d}.pgm"), "wb") as f:
+                    f.write(b"P5\n%d %d\n255\n" % (W, H))
+                    f.write(w.tobytes())
+    out = {"geometry": {"width": W, "height": H, "hdr": bool(hdr), "peak": peak, "frames": len(frames)},
+           "settings": dict(st, black_level=float(black), white_level=float(white)),
+           "warmup_pairs": [s["pair"] for s in sched if s["pair"] is not None and not s["evaluated"]],
+           "pairs": rows, "clip": clip, "scene_cuts": cuts if detect_scene_cuts else None}
+    if guard:
+        out["guard"] = {"tile": guard[0], "lo_q4": guard[1], "hi_q4": guard[2]}
+    return out
 
 
 # ---- confidence without a truth frame: the disagreement of the two warped halves at the real output schedule ----
@@ -680,8 +777,13 @@ def parse_args(argv=None):
                     help="no leave-one-out: every frame is a source, and the disagreement of the two warped halves is reported for every output of "
                          "the real schedule (--target-fps); no output frame is made")
     ap.add_argument("--target-fps", type=float, default=None, help="with --confidence: the output rate whose blending scalars are judged")
+    ap.add_argument("--guard", default=None, metavar="TILE:LO:HI",
+                    help="also produce every withheld frame with the guarded blend (a cross-fade where the warped halves disagree) and judge it by the "
+                         "same metrics: tile 16, 32 or 64, thresholds in sixteenths of an 8-bit code of mean luma difference, for example 16:32:96; "
+                         "no default, measure them on your material")
     ap.add_argument("--map-dir", default=None, metavar="DIR",
-                    help="with --map, --ssim-map or --disagreement: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; host work); with --sweep one sub-directory per setting")
+                    help="with --map, --ssim-map, --disagreement or --guard: write one PGM heat map per evaluated pair (Y plane, one pixel per tile; with "
+                         "--guard the luma mask, one pixel per luma pixel; host work); with --sweep one sub-directory per setting")
     ap.add_argument("--report", default=None, help="write the reports as JSON")
     a = ap.parse_args(argv)
     if a.pix_fmt is None:
@@ -690,13 +792,18 @@ def parse_args(argv=None):
         a.hdr = True
     elif a.hdr:
         ap.error(f"--pix-fmt {a.pix_fmt} is an 8-bit format, --hdr needs p010 or yuv420p10le")
-    if a.map_dir and not a.map and not a.ssim_map and not a.disagreement:
-        ap.error("--map-dir needs --map TILE, --ssim-map TILE or --disagreement TILE")
+    if a.guard is not None:
+        try:
+            a.guard = parse_guard(a.guard)
+        except ValueError as e:
+            ap.error(f"--{e}")
+    if a.map_dir and not a.map and not a.ssim_map and not a.disagreement and not a.guard:
+        ap.error("--map-dir needs --map TILE, --ssim-map TILE, --disagreement TILE or --guard TILE:LO:HI")
     if a.confidence and not (a.target_fps and a.target_fps > 0):
         ap.error("--confidence needs --target-fps F")
     if a.confidence:   # no truth, no output frame, no levels: what only the leave-one-out run can honour is refused, not ignored
         given = [name for name, on in (("--ssim", a.ssim), ("--map", a.map), ("--ssim-map", a.ssim_map), ("--map-dir", a.map_dir),
-                                       ("--detect-cuts", a.detect_cuts), ("--black", a.black != 0.0), ("--white", a.white != 255.0)) if on]
+                                       ("--guard", a.guard), ("--detect-cuts", a.detect_cuts), ("--black", a.black != 0.0), ("--white", a.white != 255.0)) if on]
         if given:
             ap.error(f"--confidence does not take {', '.join(given)}")
     elif a.target_fps is not None:
@@ -739,7 +846,7 @@ def main(argv=None, device=None):
         map_dir = a.map_dir and (os.path.join(a.map_dir, f"setting{k:02d}") if len(a.sweeps) > 1 else a.map_dir)
         rep = evaluate(frames, clip.hdr, clip.height, clip.width, black=a.black, white=a.white, detect_scene_cuts=a.detect_cuts,
                        scene_threshold=a.scene_threshold, source_frame_time=int(round(1e7 / clip.source_fps)), device_index=a.device,
-                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, ssim_map=a.ssim_map, disagreement=a.disagreement, **st)
+                       device=device, ssim=a.ssim, error_map=a.map, map_dir=map_dir, ssim_map=a.ssim_map, disagreement=a.disagreement, guard=a.guard, **st)
         reports.append(rep)
         c = rep["clip"]
         knobs = " ".join(f"{k}={st[k]}" for k in SETTINGS)
@@ -754,7 +861,9 @@ def main(argv=None, device=None):
                   f"{_ss(c['worst_tile_ssim']['ssim'])}" if a.ssim_map and c.get("worst_tile_ssim") else "") + (
                   f"  worst disagreement pair {c['worst_tile_disagreement']['pair']} at ({c['worst_tile_disagreement']['x']}, "
                   f"{c['worst_tile_disagreement']['y']})" + (f"  overlap Y {_ss(c['disagreement']['Y']['overlap_top1pct'])}" if a.map == a.disagreement else "")
-                  if a.disagreement else ""))
+                  if a.disagreement else "") + (
+                  f"  guarded Y {_db(c['guarded']['Y']['psnr'])} dB  guard gain {_db(c['guard_gain_db'])} dB  mean weight {c['guarded']['mask']['mean_weight']:.4f}"
+                  + (f"  guarded SSIM Y {_ss(c['guarded']['Y']['ssim'])}" if a.ssim else "") if a.guard else ""))
     if a.report:
         with open(a.report, "w") as f:
             json.dump({"input": a.input, "reports": reports}, f, indent=1)

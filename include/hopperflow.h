@@ -525,6 +525,42 @@ int hf_frame_ssim_map_enqueue(hf_ctx* ctx, int n, const void* const* device_a, c
 #define HF_MAX_DISAGREEMENT_OUTPUTS 24   /* = HF_MAX_PERIOD_OUTPUTS_WIDE */
 int hf_warp_disagreement_map_enqueue(hf_ctx* ctx, int n_t, const float* t, int tile, void* device_maps);
 
+/* ---- Guarded blend: a cross-fade where the warped halves disagree (artifact masking) ----
+ * HF_MODE_BLENDED_FRAME mixes the two warped halves everywhere, however far apart they are; where the flow is wrong that is a torn
+ * picture.  This call acts on the disagreement maps above: per output it writes the motion-compensated blend where the halves agree and
+ * fades into the plain cross-fade of the two source frames -- a soft ghost instead of a tear -- where they do not.  The reference has no
+ * counterpart; the definition is this one, in integers.  Step by step:
+ *   1. Sources.  Exactly what hf_warp_disagreement_map_enqueue reads at the same moment: frames N-2 and N-1 of ctx's ring and the
+ *      previous blurred flow.
+ *   2. Maps.  device_maps is caller-owned, n_t bytes_per_map bytes, 16-byte aligned; after the call it holds byte for byte what
+ *      hf_warp_disagreement_map_enqueue(ctx, n_t, t, tile, device_maps) stores (that launch runs first), so the confidence comes free.
+ *   3. Tile weight, per tile (ty, tx) of the LUMA plane of map k, in 64-bit integers:  cnt = the luma pixels of the tile inside the
+ *      frame (edge tiles are partial);  m = (16 sad) / (cnt << (hdr ? 8 : 0)), floor -- the mean absolute difference in sixteenths of an
+ *      8-bit code, so one 10-bit code of a P010 frame is 4 units;  wt = 0 if m <= lo_q4,  256 if m >= hi_q4,  else
+ *      ((m - lo_q4) 256) / (hi_q4 - lo_q4), floor.  The chroma planes of the map are not consulted.
+ *   4. Element weight: the tile weights interpolated bilinearly between the nominal tile centres.  With tile = 1 << lg, for a luma
+ *      element (x, y):  u = x - tile / 2,  tx0 = u >> lg (arithmetic shift),  fx = u & (tile - 1),  tx1 = tx0 + 1, both indices clamped
+ *      to [0, tw - 1];  v, ty0, fy, ty1 the same way from y;
+ *          w = ((tile - fx)(tile - fy) wt00 + fx (tile - fy) wt10 + (tile - fx) fy wt01 + fx fy wt11 + tile tile / 2) >> (2 lg)
+ *      (wtXY: column txX, row tyY).  An element (cx, cy) of the interleaved UV plane takes the weight of luma position
+ *      (cx & ~1, 2 cy); U and V share it.  0 <= w <= 256.
+ *   5. Output.  G = (M (256 - w) + Z w + 128) >> 8, with M the value hf_warp_frames(ctx, t[k], HF_MODE_BLENDED_FRAME) writes at that
+ *      element, output levels included, and Z the value the same call writes there when the blurred flow is all zeros: the cross-fade,
+ *      with the warp's edge rule as it is.  w = 0 gives M exactly, w = 256 gives Z exactly.
+ *   6. device_out[k] is a caller-owned frame of output_frame_bytes, NV12 / P010 at the output stride whatever HF_FLAG_PLANAR_* say.
+ *      Every element of columns [0, W) of every row is written; the padding columns are unspecified.
+ *   7. The identity that defines it: frame k is the mix of step 5 of the two frames that hf_warp_frames(t[k], 2) writes with the flow as
+ *      it is and after hf_write_blurred_flow(ctx, 0, zeros), by the weights of steps 3 and 4 from the map of step 2.
+ * Ordering and state are those of hf_warp_disagreement_map_enqueue: the call only enqueues, behind every update, chain, warp and copy of
+ * ctx (a batch member on its batch's stream), the next asynchronous upload into frame N-2's slot waits for it, and nothing observable
+ * of ctx changes.  (lo_q4, hi_q4) = (4080, 4081) is GUARD OFF: m never exceeds 4080 in SDR, and reaches 4081 in HDR only where the mean
+ * difference of a tile is at least 65296 of 65535 codes (black against white).  No thresholds are recommended: measure them on your material (quality.py --guard).
+ * HF_ERR_INVALID_ARGUMENT with nothing enqueued and no byte of device_maps or of any device_out[k] written: everything
+ * hf_warp_disagreement_map_enqueue refuses, a NULL device_out or device_out[k], thresholds outside 0 <= lo_q4 < hi_q4 <= 65535.
+ * Additive to ABI version 6. */
+int hf_guarded_blend_enqueue(hf_ctx* ctx, int n_t, const float* t, int tile, int lo_q4, int hi_q4,
+                             void* device_maps, void* const* device_out);
+
 /* Device-to-device copy of the output frame into caller-owned device memory. */
 int hf_download_frame_device(hf_ctx* ctx, void* device_out);
 /* Redirect warp/copy output into caller-owned device memory (NULL restores the internal buffer).  HF_FLAG_PLANAR_OUT: the kernels
